@@ -18,16 +18,25 @@ One *step* = explaining ``--instances`` instances per GPU (weak scaling:
 per-GPU work fixed as N grows; whole-job value = N * instances / step_time).
 Launched by the driver as  torchrun --nnodes=1 --nproc-per-node N bench.py
 --gpus N ...  (one rank per GPU over RCCL).
+
+A plain run sets up, warms up, times ``--steps`` steps and prints one JSON
+result line. ``--dump-outputs DIR`` additionally writes what the last timed
+step returned as ``DIR/<name>.npy``. Everything that takes runs of its own
+(today: the fp64 self-check behind ``max_phi_err_vs_fp64``) only runs with
+``--full``.
 """
 from __future__ import annotations
 
 import argparse
 import json
+import os
 import time
 
 import numpy as np
 
 BASELINE_EXPL_PER_S = 20.5  # reference best single-node (125.05 s / 2560, BASELINE.md)
+
+DUMP_BYTES_MAX = 64 * 1024 * 1024  # --dump-outputs budget, all files together
 
 CONFIG_DEFAULTS = {
     "adult": {"instances": 2560, "background": 100},
@@ -92,6 +101,41 @@ def build_problem(cfg: str, args, rank: int):
     raise ValueError(cfg)
 
 
+def dump_outputs(out, directory: str) -> None:
+    """Write what the last timed step returned as ``<name>.npy`` files.
+
+    Single-process steps return the per-class list of ``(instances, groups)``
+    arrays -> ``shap_values_<class>.npy``; collective steps return the gathered
+    ``(instances, groups, classes)`` tensor -> ``shap_values.npy``. Values keep
+    float32/float64 as computed. An output set above DUMP_BYTES_MAX is cut to a
+    fixed, seeded, sorted sample of rows (the same rows for every array and
+    every run with the same arguments)."""
+    if isinstance(out, (list, tuple)):
+        named = {f"shap_values_{o}": a for o, a in enumerate(out)}
+    else:
+        named = {"shap_values": out}
+    arrays = {}
+    for name, a in named.items():
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32)
+        arrays[name] = a
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        n_rows = min(a.shape[0] for a in arrays.values())
+        row_bytes = sum(a.nbytes // a.shape[0] for a in arrays.values())
+        keep = max(1, DUMP_BYTES_MAX // row_bytes)
+        rows = np.sort(
+            np.random.default_rng(0).choice(n_rows, size=keep, replace=False)
+        )
+        arrays = {name: a[rows] for name, a in arrays.items()}
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main() -> None:
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -111,11 +155,23 @@ def main() -> None:
                         "plain bf16 (fastest), or fp64 (full-double "
                         "verification mode, linear predictors)")
     p.add_argument("--selfcheck", type=int, default=64, metavar="K",
-                   help="after timing, re-explain the first K instances in "
-                        "the fp64 device mode (same masks) and report "
-                        "max_phi_err_vs_fp64 in the JSON; 0 disables "
+                   help="with --full: after timing, re-explain the first K "
+                        "instances in the fp64 device mode (same masks) and "
+                        "report max_phi_err_vs_fp64 in the JSON; 0 disables "
                         "(linear-predictor configs only)")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline figure that "
+                        "takes runs of its own (the --selfcheck fp64 "
+                        "comparison); a plain run only times the steps")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step returned as DIR/<name>.npy (float32/float64, "
+                        "at most 64 MB in all)")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.warmup < 0:
+        p.error("--warmup must not be negative")
     defaults = CONFIG_DEFAULTS[args.config]
     if args.instances is None:
         args.instances = defaults["instances"]
@@ -202,10 +258,9 @@ def main() -> None:
             )
             counts = [args.instances] * world
             return allgather_rows(sv, counts)
-        sv = engine.shap_values(
+        return engine.shap_values(
             X=X_in, instance_offset=rank * args.instances, **ekw
         )
-        return sv[0]
 
     def sync():
         if use_cuda:
@@ -239,8 +294,11 @@ def main() -> None:
     # precision self-certification: re-explain a prefix
     # of this rank's shard in the fp64 device mode — identical masks via the
     # counter RNG — and report the measured fp32-pipeline error bound
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
+
     max_phi_err = None
-    if (args.selfcheck and use_cuda and args.dtype != "fp64"
+    if (args.full and args.selfcheck and use_cuda and args.dtype != "fp64"
             and isinstance(pred, LinearPredictor)):
         k = min(args.selfcheck, args.instances)
         off = rank * args.instances
@@ -297,7 +355,9 @@ def main() -> None:
                 "nsamples": args.nsamples or "default(2M+2048)",
                 "parallelism": f"dp{n_gpus}",
                 "device": device,
-                "out_shape": list(out.shape),
+                "out_shape": list(
+                    (out[0] if isinstance(out, list) else out).shape
+                ),
             },
         }
         print(json.dumps(result))

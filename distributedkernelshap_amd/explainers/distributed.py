@@ -75,6 +75,14 @@ def _worker_main(worker_id, explainer_type, init_args, init_kwargs, task_q,
     CUDA replicas are pinned round-robin to the node's GPUs via
     HIP_VISIBLE_DEVICES — set before torch is imported in this process
     (spawn context; torch is only imported lazily by the replica ctor)."""
+    import signal
+    import sys
+
+    # An idle worker blocks in task_q.get() holding the queue's shared reader
+    # lock. Turn SIGTERM (Process.terminate) into SystemExit so the lock is
+    # released on the way out; the default action would kill the process with
+    # the lock held and starve every surviving worker.
+    signal.signal(signal.SIGTERM, lambda signum, frame: sys.exit(0))
     try:
         if init_kwargs.get("device") == "cuda":
             import os

@@ -22,7 +22,7 @@ def _run(args, timeout=600, env_extra=None):
 
 def test_bench_json_contract(tmp_path):
     r = _run(["bench.py", "--instances", "8", "--steps", "1", "--warmup", "0",
-              "--device", "cpu"])
+              "--device", "cpu", "--full"])
     assert r.returncode == 0, r.stderr[-800:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     obj = json.loads(line)
@@ -36,6 +36,58 @@ def test_bench_json_contract(tmp_path):
     assert "2560 inst" not in obj["metric"]
     assert obj["vs_baseline"] is None
     assert "max_phi_err_vs_fp64" in obj
+
+
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's shap values, and two runs
+    with the same arguments see the same inputs and write the same arrays."""
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        r = _run(["bench.py", "--instances", "8", "--steps", "2", "--warmup",
+                  "0", "--device", "cpu", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-800:]
+        line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
+        obj = json.loads(line)
+        assert obj["steps"] == 2 and obj["ms_per_step"] > 0
+        # a plain run does not run the fp64 self-check
+        assert obj["max_phi_err_vs_fp64"] is None
+        assert sorted(os.listdir(d)) == ["shap_values_0.npy", "shap_values_1.npy"]
+        dumps.append([np.load(d / f) for f in sorted(os.listdir(d))])
+    for a, b in zip(*dumps):
+        assert a.dtype in (np.float32, np.float64)
+        assert a.shape == (8, 12)
+        assert np.isfinite(a).all() and np.abs(a).max() > 0
+        assert np.array_equal(a, b)
+
+
+def test_bench_dump_outputs_size_cap(tmp_path, monkeypatch):
+    """Outputs above the byte budget are cut to a fixed seeded row sample,
+    the same rows in every array and on every call."""
+    import numpy as np
+
+    monkeypatch.syspath_prepend(os.path.abspath(ROOT))
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 4096)
+    rng = np.random.default_rng(3)
+    out = [rng.normal(size=(1000, 12)).astype(np.float32) for _ in range(2)]
+    bench.dump_outputs(out, str(tmp_path / "a"))
+    bench.dump_outputs(out, str(tmp_path / "b"))
+    a = [np.load(tmp_path / "a" / f"shap_values_{o}.npy") for o in range(2)]
+    b = [np.load(tmp_path / "b" / f"shap_values_{o}.npy") for o in range(2)]
+    assert sum(x.nbytes for x in a) <= 4096
+    assert a[0].shape == a[1].shape and 1 <= a[0].shape[0] < 1000
+    for o in range(2):
+        assert a[o].dtype == np.float32
+        assert np.array_equal(a[o], b[o])
+        # sampled rows are rows of the full output, in order
+        idx = [int(np.flatnonzero((out[o] == row).all(axis=1))[0]) for row in a[o]]
+        assert idx == sorted(idx)
+    assert [int(np.flatnonzero((out[0] == r).all(axis=1))[0]) for r in a[0]] == \
+        [int(np.flatnonzero((out[1] == r).all(axis=1))[0]) for r in a[1]]
 
 
 def test_pool_cli_writes_results(tmp_path):
