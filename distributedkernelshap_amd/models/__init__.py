@@ -1,2 +1,7 @@
-from .predictors import LinearPredictor, TorchPredictor, make_predictor  # noqa: F401
+from .predictors import (  # noqa: F401
+    LinearPredictor,
+    MLPPredictor,
+    TorchPredictor,
+    make_predictor,
+)
 from .synthetic import SyntheticData, make_adult_like, make_tabular  # noqa: F401

@@ -5,6 +5,7 @@ Per instance-bucket (instances sharing a varying-group pattern):
   enum masks (host, cached per plan)  ──┐
   fill_random_masks  (HIP K2, Philox)  ─┴─> masks (B,S,M) u8 on device
   fused_predict_linear (HIP K3-K6, MFMA)  -> ey (B,S,n_out)   [linear predictor]
+     — or — fused_predict_mlp (HIP K4m, MFMA)  -> ey        [MLP predictor]
      — or — synth_chunk (HIP K3') + torch module + weighted mean  [torch predictor]
   link transform (torch, fp32)           -> eyAdj
   wls_solve (HIP K7)                     -> phi (B,M,n_out)
@@ -81,6 +82,8 @@ class GpuKernelShap:
 
         self.linear = None
         self.module = None
+        self.mlp = None          # fp64 weights + operand images (MLPPredictor)
+        self.mlp_fused = False   # True when fused_predict_mlp serves this engine
         lp = getattr(engine.predictor, "linear_params", None)
         if lp is not None:
             W, b, act = lp()
@@ -95,6 +98,8 @@ class GpuKernelShap:
             bg_part.index_add_(1, self.col_group, contrib)
             self.bg_part = bg_part
             self.baseN = self.bg @ self.linear["W"].T + self.linear["b"]  # (N, o)
+        elif getattr(engine.predictor, "mlp_params", None) is not None:
+            self._init_mlp(engine.predictor)
         else:
             tm = getattr(engine.predictor, "torch_module", None)
             if tm is not None:
@@ -159,6 +164,163 @@ class GpuKernelShap:
         return buf
 
     # ------------------------------------------------------------------ #
+    # MLPPredictor: fused_predict_mlp (K4m) with the torch module as the
+    # out-of-envelope fallback
+
+    def _init_mlp(self, predictor):
+        import copy
+
+        from . import mlp_pack
+
+        t = self.torch
+        kc = self.engine.kernels
+        if kc.predict_dtype not in ("fp32", "bf16", "fp64"):
+            raise ValueError(
+                f"predict_dtype={kc.predict_dtype!r} is not available for "
+                "MLPPredictor; supported: 'fp32', 'bf16' (fused MLP kernel) "
+                "and 'fp64' (verification)"
+            )
+        W, b, hid, act = predictor.mlp_params()
+        self.mlp = {
+            "W64": [t.tensor(np.asarray(w), dtype=t.float64, device=self.device)
+                    for w in W],
+            "b64": [t.tensor(np.asarray(v), dtype=t.float64, device=self.device)
+                    for v in b],
+            "hid": hid,
+            "act": act,
+        }
+        # every module-path consumer (fallback, sample-sharded, autocast)
+        # keeps working; a private copy so the predictor's own stays on CPU
+        self.module = copy.deepcopy(predictor.torch_module()).to(self.device)
+        self._mlp_logged = False
+        if kc.predict_dtype == "fp64":
+            # verification mode: unrounded fit-time constants
+            eng = self.engine
+            self.mlp["bg64"] = t.tensor(
+                eng.background, dtype=t.float64, device=self.device)
+            self.mlp["wbg64"] = t.tensor(
+                eng.bg_weights, dtype=t.float64, device=self.device)
+            self.mlp["fnull64"] = t.tensor(
+                eng.fnull, dtype=t.float64, device=self.device)
+            return
+        dtype = t.bfloat16 if kc.predict_dtype == "bf16" else t.float32
+        reason = (None if kc.fused_predict
+                  else "kernels.fused_predict is off")
+        reason = reason or mlp_pack.envelope_reason(W, hid, dtype)
+        if reason is not None:
+            self._mlp_log_fallback(reason)
+            return
+        pack = mlp_pack.pack_mlp_weights(W, b, dtype, self.device)
+        bg64 = self.bg.double()
+        self.mlp["pack"] = pack
+        # fit-time constants shared by all instances
+        self.mlp["bgpart1"] = mlp_pack.group_parts(
+            pack, bg64, self.col_group, self.n_groups)      # (N, H1pad, G)
+        self.mlp["base1"] = mlp_pack.base1(pack, bg64)      # (N, H1pad)
+        self.mlp["bg_img"] = {}
+        self.mlp_fused = True
+
+    def _mlp_log_fallback(self, reason):
+        if not self._mlp_logged:
+            logger.info(
+                "MLPPredictor runs on the torch-module path, not the fused "
+                "MLP kernel: %s", reason,
+            )
+            self._mlp_logged = True
+
+    def _mlp_forward_f64(self, rows64):
+        """fp64 torch forward from the fp64 weights."""
+        t = self.torch
+        h = rows64
+        ws, bs = self.mlp["W64"], self.mlp["b64"]
+        for w, b in zip(ws[:-1], bs[:-1]):
+            h = h @ w.T + b
+            if self.mlp["hid"] == "relu":
+                h = t.relu(h)
+            elif self.mlp["hid"] == "tanh":
+                h = t.tanh(h)
+        z = h @ ws[-1].T + bs[-1]
+        if self.mlp["act"] == "softmax":
+            return t.softmax(z, dim=-1)
+        if self.mlp["act"] == "sigmoid":
+            return t.sigmoid(z)
+        return z
+
+    def _ey_fused_mlp(self, masks, X_dev, varying):
+        """K4m: fused MLP predict. Only ey (B,S,n_out) reaches HBM; the
+        workspaces are the first-layer operand images xp1 (B,H1pad,Mpad) and
+        bgp1n (N,H1pad,Mpad), the latter cached per varying pattern."""
+        from . import mlp_pack
+
+        t = self.torch
+        b, s, m = masks.shape
+        mlp = self.mlp
+        pack = mlp["pack"]
+        vidx = t.tensor(varying, dtype=t.int64, device=self.device)
+        key = np.asarray(varying).tobytes()
+        bgp1n = mlp["bg_img"].get(key)
+        if bgp1n is None:
+            if len(mlp["bg_img"]) >= 8:
+                mlp["bg_img"].clear()
+            bgp1n = mlp_pack.first_layer_image(
+                pack, mlp["bgpart1"], vidx, negate=True)
+            mlp["bg_img"][key] = bgp1n
+        xparts = mlp_pack.group_parts(
+            pack, X_dev.double(), self.col_group, self.n_groups)
+        xp1 = mlp_pack.first_layer_image(pack, xparts, vidx)
+        ey = self._buf("ey", (b, s, self.n_out))
+        self.ext.fused_predict_mlp(
+            masks.contiguous(), xp1, bgp1n, mlp["base1"], pack["hidden_w"],
+            pack["hidden_b"], pack["wout"], pack["bout"], self.bg_w, ey,
+            mlp_pack.ACT_CODE[mlp["act"]], 0,
+        )
+        return ey
+
+    def _ey_predict_nonlinear(self, masks, X_dev, varying):
+        """ey for non-linear predictors, shared by the bucket loop and the
+        sample-sharded path: the fused MLP kernel when it applies, else the
+        synth + torch-module path."""
+        from . import mlp_pack
+
+        if self.mlp_fused:
+            if len(varying) <= mlp_pack.MAX_GROUPS:
+                return self._ey_fused_mlp(masks, X_dev, varying)
+            self._mlp_log_fallback(
+                f"{len(varying)} varying groups (supported: <= "
+                f"{mlp_pack.MAX_GROUPS})"
+            )
+        return self._ey_torch_module(masks, X_dev, varying)
+
+    def _ey_mlp_f64(self, masks, X_dev, varying, budget_bytes=256 << 20):
+        """fp64 verification path for MLPPredictor (predict_dtype='fp64'):
+        explicit masked blend + fp64 torch MLP on the SAME device masks,
+        chunked over samples like ``_ey_linear_f64``."""
+        t = self.torch
+        b, s, m = masks.shape
+        vmap = np.full(self.n_groups, m, dtype=np.int64)
+        for i, g in enumerate(varying):
+            vmap[g] = i
+        colk = t.tensor(vmap[self.engine._col_group], device=self.device)
+        bg = self.mlp["bg64"]
+        X64 = X_dev.double()
+        wbg64 = self.mlp["wbg64"]
+        width = max([self.D] + [w.shape[0] for w in self.mlp["W64"]])
+        s_chunk = max(1, budget_bytes // (8 * 3 * b * self.N * width))
+        ey = t.empty(b, s, self.n_out, dtype=t.float64, device=self.device)
+        zero_col = t.zeros(b, 1, 1, dtype=t.bool, device=self.device)
+        for lo in range(0, s, s_chunk):
+            hi = min(lo + s_chunk, s)
+            mk = masks[:, lo:hi].bool()
+            # non-varying columns map to an always-off sentinel column m
+            mk = t.cat([mk, zero_col.expand(b, hi - lo, 1)], dim=2)[:, :, colk]
+            rows = t.where(
+                mk[:, :, None, :], X64[:, None, None, :], bg[None, None, :, :]
+            )                                             # (b, sc, N, D)
+            p = self._mlp_forward_f64(rows)
+            ey[:, lo:hi] = t.einsum("bsno,n->bso", p, wbg64)
+        return ey
+
+    # ------------------------------------------------------------------ #
 
     def _link(self, p):
         t = self.torch
@@ -181,6 +343,8 @@ class GpuKernelShap:
             if a == 2:
                 return t.softmax(z, dim=-1)
             return z
+        if self.mlp is not None:
+            return self._mlp_forward_f64(rows.double())
         with t.no_grad():
             return self.module(rows).double()
 
@@ -658,6 +822,11 @@ class GpuKernelShap:
             mpad = max(4, (g + 3) // 4 * 4)
             per_inst += 4 * mpad * npad * max(1, self.n_out) # diff image
             per_inst += 8 * g * (g + self.n_out) * 2         # Gram + LU work
+        if self.mlp_fused:
+            # fused MLP workspaces: fp64 group parts (D x G indicator product
+            # and H1pad x G result) + the xp1 operand image (H1pad x Mpad)
+            h1 = self.mlp["pack"]["hpad"][0]
+            per_inst += 8 * g * (self.D + 2 * h1) + 4 * h1 * (g + 31)
         return max(1, self._CHUNK_BYTES // per_inst)
 
     def shap_values(
@@ -718,9 +887,17 @@ class GpuKernelShap:
         timer.mark("h2d")
 
         fp64 = self.engine.kernels.predict_dtype == "fp64"
-        fx = self._predict_rows_f64(X_dev)              # (B, n_out) fp64
+        X64_dev = None
+        if fp64 and self.mlp is not None:
+            # MLP verification mode: inputs stay fp64 end to end (the fp32
+            # rounding of x alone shifts phi by ~1e-7)
+            X64_dev = (X.to(self.device).double() if t.is_tensor(X)
+                       else t.tensor(X, dtype=t.float64, device=self.device))
+        fx = self._predict_rows_f64(                    # (B, n_out) fp64
+            X_dev if X64_dev is None else X64_dev)
         lfx = self._link(fx)
-        lfnull64 = self._link(self.fnull.double())
+        lfnull64 = self._link(
+            self.fnull.double() if X64_dev is None else self.mlp["fnull64"])
         total_all = (lfx - lfnull64[None, :])           # (B, n_out) fp64
         if not fp64:
             total_all = total_all.float()
@@ -857,8 +1034,9 @@ class GpuKernelShap:
             sub_X = X_dev[ids_t]
             if fp64:
                 phi = self._bucket_fp64(
-                    plan, masks, sub_X, varying, ids_t, total_all, lfnull64,
-                    l1_reg,
+                    plan, masks,
+                    sub_X if X64_dev is None else X64_dev[ids_t],
+                    varying, ids_t, total_all, lfnull64, l1_reg,
                 )
                 timer.mark("wls")
                 vidx_t = t.tensor(varying, dtype=t.int64, device=self.device)
@@ -908,7 +1086,7 @@ class GpuKernelShap:
             else:
                 if packed is not None:
                     self.ext.pack_masks(masks, packed)
-                ey = self._ey_torch_module(masks, sub_X, varying)
+                ey = self._ey_predict_nonlinear(masks, sub_X, varying)
             timer.mark("predict")
             ey_adj = self._link_ey(ey, lfnull, pairwise)
             total = total_all[ids_t].contiguous()
@@ -1031,14 +1209,17 @@ class GpuKernelShap:
         device masks, exact fp64 kernel weights (rebuilt from the plan's
         fp64 arrays, not the fp32 device copy), fp64 link and WLS."""
         t = self.torch
-        if self.linear is None:
+        if self.linear is None and self.mlp is None:
             raise TypeError(
                 "predict_dtype='fp64' is the linear-predictor verification "
                 "mode; torch-module predictors have no fp64 reference "
                 "(convert the module to double and use device='cpu' instead)."
             )
         b = sub_X.shape[0]
-        ey = self._ey_linear_f64(masks, sub_X, varying)
+        if self.mlp is not None:
+            ey = self._ey_mlp_f64(masks, sub_X, varying)
+        else:
+            ey = self._ey_linear_f64(masks, sub_X, varying)
         kw64 = t.from_numpy(
             np.concatenate([
                 plan.enum_weights,
@@ -1047,7 +1228,7 @@ class GpuKernelShap:
             ])
         ).to(self.device)
         kw = kw64[None, :].expand(b, plan.nsamples).contiguous()
-        act3 = self._act_oimg()[0] == 3
+        act3 = self.linear is not None and self._act_oimg()[0] == 3
         if self.link_name == "identity":
             ey_adj = ey - lfnull64[None, None, :]
         elif act3 and self.n_out == 2:

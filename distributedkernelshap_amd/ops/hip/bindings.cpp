@@ -1,4 +1,5 @@
-// Torch bindings for the CDNA4 KernelSHAP kernels (kshap_kernels.hip).
+// Torch bindings for the CDNA4 KernelSHAP kernels (kshap_kernels.hip,
+// mlp_kernels.hip).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <c10/hip/HIPStream.h>
@@ -66,6 +67,15 @@ extern "C" int launch_fused_predict_tiled_bf16(
     const uint8_t* masksU, const uint16_t* diffB, const float* base,
     const float* wbg, float* partial, float* ey, int B, int S, int M,
     int Mpad, int Npad, int n_out, int act, int split, hipStream_t stream);
+
+// mlp_kernels.hip
+extern "C" int launch_fused_predict_mlp(
+    const uint8_t* masks, const void* xp1, const void* bgp1n,
+    const float* base1, const void* const* hw, const float* const* hb,
+    const int* H, int nhid, const void* wout, const float* bout,
+    const float* wbg, float* ey, int B, int S, int M, int Mpad, int N,
+    int n_out, int act, int hidden_act, int is_bf16, int nsplit,
+    hipStream_t stream);
 
 namespace {
 
@@ -324,9 +334,80 @@ void fused_predict_tiled_bf16(
                          "(Mpad%32==0, Npad%16==0, n_out in {1,2,4})");
 }
 
+void fused_predict_mlp(
+    torch::Tensor masks, torch::Tensor xp1, torch::Tensor bgp1n,
+    torch::Tensor base1, std::vector<torch::Tensor> hidden_w,
+    std::vector<torch::Tensor> hidden_b, torch::Tensor wout,
+    torch::Tensor bout, torch::Tensor wbg, torch::Tensor ey, int64_t act,
+    int64_t hidden_act) {
+    static const char* envelope =
+        "fused_predict_mlp: outside the supported envelope (1-3 relu hidden "
+        "layers of padded width <= 256, n_out <= 8, M <= Mpad <= 64, widths "
+        "padded to 16 (fp32) / 32 (bf16))";
+    CHECK_DEV(masks); CHECK_DEV(xp1); CHECK_DEV(bgp1n); CHECK_DEV(base1);
+    CHECK_DEV(wout); CHECK_DEV(bout); CHECK_DEV(wbg); CHECK_DEV(ey);
+    TORCH_CHECK(masks.dtype() == torch::kUInt8 && masks.dim() == 3,
+                "masks must be u8 (B,S,M)");
+    const bool bf16 = xp1.dtype() == torch::kBFloat16;
+    TORCH_CHECK(bf16 || xp1.dtype() == torch::kFloat32,
+                "operand images must be float32 or bfloat16");
+    const auto wdt = xp1.dtype();
+    TORCH_CHECK(hidden_w.size() == hidden_b.size(), "hidden_w vs hidden_b");
+    TORCH_CHECK(hidden_w.size() + 1 <= 3, envelope);
+    const int nhid = (int)hidden_w.size() + 1;
+    TORCH_CHECK(xp1.dim() == 3 && bgp1n.dim() == 3 && base1.dim() == 2
+                && wout.dim() == 3 && ey.dim() == 3, "operand ranks");
+    int B = masks.size(0), S = masks.size(1), M = masks.size(2);
+    int H[3] = {(int)xp1.size(1), 0, 0};
+    int Mpad = xp1.size(2), N = bgp1n.size(0), n_out = ey.size(2);
+    TORCH_CHECK(xp1.size(0) == B, "xp1 must be (B,H1,Mpad)");
+    TORCH_CHECK(bgp1n.dtype() == wdt && bgp1n.size(1) == H[0]
+                && bgp1n.size(2) == Mpad, "bgp1n must be (N,H1,Mpad)");
+    TORCH_CHECK(base1.dtype() == torch::kFloat32 && base1.size(0) == N
+                && base1.size(1) == H[0], "base1 must be f32 (N,H1)");
+    const void* hw[2] = {nullptr, nullptr};
+    const float* hb[2] = {nullptr, nullptr};
+    for (int l = 1; l < nhid; ++l) {
+        const torch::Tensor& w = hidden_w[l - 1];
+        const torch::Tensor& bb = hidden_b[l - 1];
+        CHECK_DEV(w); CHECK_DEV(bb);
+        TORCH_CHECK(w.dtype() == wdt && w.dim() == 2 && w.size(1) == H[l - 1],
+                    "hidden weight must be (H_out, H_in) in the operand dtype");
+        H[l] = w.size(0);
+        TORCH_CHECK(bb.dtype() == torch::kFloat32 && bb.dim() == 1
+                    && bb.size(0) == H[l], "hidden bias must be f32 (H_out)");
+        hw[l - 1] = w.data_ptr();
+        hb[l - 1] = bb.data_ptr<float>();
+    }
+    const int nsplit = wout.size(0);
+    TORCH_CHECK(wout.dtype() == wdt && wout.size(1) == 16
+                && wout.size(2) == H[nhid - 1], "wout must be (nsplit,16,H_last)");
+    TORCH_CHECK(bout.dtype() == torch::kFloat32 && bout.numel() == 16,
+                "bout must be f32 (16)");
+    TORCH_CHECK(wbg.dtype() == torch::kFloat32 && wbg.numel() == N, "wbg must be f32 (N)");
+    TORCH_CHECK(ey.dtype() == torch::kFloat32 && ey.size(0) == B
+                && ey.size(1) == S, "ey must be f32 (B,S,n_out)");
+    int rc = launch_fused_predict_mlp(
+        masks.data_ptr<uint8_t>(), xp1.data_ptr(), bgp1n.data_ptr(),
+        base1.data_ptr<float>(), hw, hb, H, nhid, wout.data_ptr(),
+        bout.data_ptr<float>(), wbg.data_ptr<float>(), ey.data_ptr<float>(),
+        B, S, M, Mpad, N, n_out, (int)act, (int)hidden_act, bf16 ? 1 : 0,
+        nsplit, current_stream());
+    TORCH_CHECK(rc != -2, "fused_predict_mlp: LDS size attribute rejected");
+    TORCH_CHECK(rc == 0, envelope);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+    m.def("fused_predict_mlp", &fused_predict_mlp,
+          "fused MLP predict (K4m): first layer folded over varying groups, "
+          "hidden activations in LDS, f32 or bf16 MFMA by operand dtype",
+          pybind11::arg("masks"), pybind11::arg("xp1"), pybind11::arg("bgp1n"),
+          pybind11::arg("base1"), pybind11::arg("hidden_w"),
+          pybind11::arg("hidden_b"), pybind11::arg("wout"),
+          pybind11::arg("bout"), pybind11::arg("wbg"), pybind11::arg("ey"),
+          pybind11::arg("act"), pybind11::arg("hidden_act") = 0);
     m.def("fill_random_masks", &fill_random_masks,
           "Philox coalition sampling (K2)");
     m.def("fused_predict_linear", &fused_predict_linear,

@@ -143,7 +143,9 @@ def _explain_sample_sharded_gpu(
         mpad = max(4, (m + 3) // 4 * 4)
         npad = (gpu.N + 15) // 16 * 16
         if gpu.linear is None:
-            ey = gpu._ey_torch_module(sub, sub_X, varying)
+            # fused MLP kernel on this rank's slice when the predictor is
+            # an in-envelope MLPPredictor, else synth + torch module
+            ey = gpu._ey_predict_nonlinear(sub, sub_X, varying)
         elif mpad <= 64 and npad <= 128 and gpu.n_out in (1, 2, 4):
             ey = gpu._ey_fused_linear(sub.contiguous(), sub_X, varying)
         else:

@@ -126,9 +126,40 @@ def load_data(assets_dir: str = None):
     return bunch
 
 
+def _wrap_sklearn_mlp(obj):
+    """sklearn ``MLPClassifier`` / ``MLPRegressor`` -> native MLPPredictor
+    (``coefs_[i]`` is (in, out); ours are (out, in))."""
+    from ..models.predictors import MLPPredictor
+
+    hidden = obj.activation
+    if hidden not in ("relu", "tanh", "identity"):
+        raise TypeError(
+            f"sklearn MLP hidden activation {hidden!r} is not supported "
+            "(relu, tanh, identity)"
+        )
+    weights = [np.asarray(c, dtype=np.float64).T for c in obj.coefs_]
+    biases = [np.asarray(i, dtype=np.float64) for i in obj.intercepts_]
+    out = obj.out_activation_
+    if out == "softmax":
+        act = "softmax"
+    elif out == "identity":
+        act = "none"
+    elif out == "logistic":
+        if weights[-1].shape[0] == 1:  # binary sigmoid == softmax([0, z])
+            weights[-1] = np.vstack([np.zeros_like(weights[-1][0]), weights[-1][0]])
+            biases[-1] = np.array([0.0, float(biases[-1][0])])
+            act = "softmax"
+        else:
+            act = "sigmoid"
+    else:
+        raise TypeError(f"sklearn MLP output activation {out!r} is not supported")
+    return MLPPredictor(weights, biases, activation=act, hidden_activation=hidden)
+
+
 def load_model(path: str = None):
     """Unpickle a predictor; sklearn LogisticRegression is wrapped into the
-    native LinearPredictor so the fused GPU path applies
+    native LinearPredictor and sklearn MLPClassifier / MLPRegressor into
+    the native MLPPredictor, so the fused GPU paths apply
     (reference ``load_model``, utils.py:137-157)."""
     import pickle
 
@@ -148,6 +179,9 @@ def load_model(path: str = None):
         else:
             w, b = coef, intercept
         return LinearPredictor(w, b, activation="softmax")
+    coefs = getattr(obj, "coefs_", None)
+    if coefs is not None and hasattr(obj, "out_activation_"):
+        return _wrap_sklearn_mlp(obj)
     if not callable(obj):
         raise TypeError(f"loaded object {type(obj)} is not a predictor")
     return obj
