@@ -2,6 +2,7 @@ from .predictors import (  # noqa: F401
     LinearPredictor,
     MLPPredictor,
     TorchPredictor,
+    TreeEnsemblePredictor,
     make_predictor,
 )
 from .synthetic import SyntheticData, make_adult_like, make_tabular  # noqa: F401

@@ -11,6 +11,10 @@ Here predictors are first-class objects:
 * ``MLPPredictor`` — feed-forward network with explicit weights; exposes
   ``mlp_params()`` so the GPU engine can run the fused MLP HIP kernel
   (first layer folded over coalition groups, hidden activations in LDS).
+* ``TreeEnsemblePredictor`` — decision-tree ensemble (gradient boosting,
+  forests) with explicit node tables; exposes ``tree_params()`` so the GPU
+  engine can run the fused tree HIP kernel (split decisions packed to bits
+  once per row, a bitwise select and a bit-register walk per sample).
 * ``TorchPredictor`` — wraps any torch ``nn.Module`` (MLP / ResNet configs);
   the GPU engine materialises synth tiles on-device and calls the module
   stream-ordered.
@@ -21,7 +25,8 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["LinearPredictor", "MLPPredictor", "TorchPredictor", "make_predictor"]
+__all__ = ["LinearPredictor", "MLPPredictor", "TorchPredictor",
+           "TreeEnsemblePredictor", "make_predictor"]
 
 
 def _softmax(z: np.ndarray) -> np.ndarray:
@@ -262,10 +267,353 @@ class MLPPredictor:
         return cls(weights, biases, activation, hidden[0] if hidden else "relu")
 
 
+class TreeEnsemblePredictor:
+    """Ensemble of binary decision trees with explicit tables:
+    ``act(base + scale · Σ_t value_t(leaf_t(x)))``.
+
+    ``trees`` is a list of dicts with per-node arrays ``feature``,
+    ``threshold``, ``left``, ``right`` (root = node 0; a node with
+    ``left < 0`` is a leaf) and ``value``: ``(n_nodes,)`` scalar leaves, the
+    tree adding into output column ``out_col[t]``, or ``(n_nodes, n_out)``
+    leaf vectors. All trees of an ensemble use the same leaf form.
+
+    The comparison rule is sklearn's: the input is rounded to float32 and
+    ``float64(x32) <= threshold`` goes left. ``__call__`` is the numpy oracle
+    with exactly this rule; ``tree_params()`` is the protocol hook the GPU
+    engine uses to run the fused ``fused_predict_trees`` HIP kernel;
+    ``torch_module()`` is the fp32 gather-traversal ``nn.Module`` used when
+    the ensemble is outside that kernel's envelope.
+
+    NaN inputs are not supported: sklearn >= 1.3 routes a missing value per
+    node (``missing_go_to_left``), which these tables do not carry.
+    ``__call__`` raises ``ValueError`` on a NaN; the GPU paths do not look.
+    """
+
+    _OUT = ("softmax", "sigmoid", "none")
+
+    def __init__(self, trees, n_features: int, n_out: int, base=None,
+                 scale: float = 1.0, out_col=None, activation: str = "none"):
+        if activation not in self._OUT:
+            raise ValueError(f"unknown activation {activation}")
+        if len(trees) < 1:
+            raise ValueError("an ensemble needs at least one tree")
+        if n_out < 1 or n_features < 1:
+            raise ValueError("n_out and n_features must be positive")
+        self.n_features = int(n_features)
+        self._n_out = int(n_out)
+        self.scale = float(scale)
+        self.activation = activation
+        self.base = (np.zeros(n_out) if base is None
+                     else np.asarray(base, dtype=np.float64).reshape(-1))
+        if self.base.shape[0] != n_out:
+            raise ValueError("base must have n_out entries")
+        self.trees = []
+        vector = None
+        for ti, tr in enumerate(trees):
+            feat = np.asarray(tr["feature"], dtype=np.int64).reshape(-1)
+            thr = np.asarray(tr["threshold"], dtype=np.float64).reshape(-1)
+            left = np.asarray(tr["left"], dtype=np.int64).reshape(-1)
+            right = np.asarray(tr["right"], dtype=np.int64).reshape(-1)
+            val = np.asarray(tr["value"], dtype=np.float64)
+            nn_ = feat.shape[0]
+            if nn_ < 1 or not (thr.shape[0] == left.shape[0] == right.shape[0]
+                               == val.shape[0] == nn_):
+                raise ValueError(f"tree {ti}: node arrays must be equally long")
+            if val.ndim not in (1, 2) or (val.ndim == 2 and val.shape[1] != n_out):
+                raise ValueError(
+                    f"tree {ti}: value must be (n_nodes,) or (n_nodes, n_out)")
+            if vector is None:
+                vector = val.ndim == 2
+            elif vector != (val.ndim == 2):
+                raise ValueError("all trees must use the same leaf form")
+            internal = left >= 0
+            if np.any(internal != (right >= 0)):
+                raise ValueError(f"tree {ti}: a node has exactly one child")
+            kids = np.concatenate([left[internal], right[internal]])
+            if np.any(kids >= nn_) or np.any(kids == 0) or \
+                    len(np.unique(kids)) != len(kids) or len(kids) != nn_ - 1:
+                raise ValueError(
+                    f"tree {ti}: children must form one tree rooted at node 0")
+            if np.any(feat[internal] < 0) or np.any(feat[internal] >= n_features):
+                raise ValueError(f"tree {ti}: split feature out of range")
+            if not np.all(np.isfinite(thr[internal])):
+                raise ValueError(f"tree {ti}: thresholds must be finite")
+            self.trees.append({
+                "feature": np.where(internal, feat, 0), "threshold": thr,
+                "left": left, "right": right, "value": val,
+            })
+        self.vector_leaves = bool(vector)
+        if self.vector_leaves:
+            if out_col is not None:
+                raise ValueError("out_col does not apply to vector leaves")
+            self.out_col = None
+        else:
+            oc = (np.zeros(len(trees), dtype=np.int64) if out_col is None
+                  else np.asarray(out_col, dtype=np.int64).reshape(-1))
+            if oc.shape[0] != len(trees) or np.any(oc < 0) or np.any(oc >= n_out):
+                raise ValueError("out_col must name one output column per tree")
+            self.out_col = oc
+        self._flat = None
+        self._module = None
+
+    @property
+    def n_out(self) -> int:
+        return self._n_out
+
+    @property
+    def n_trees(self) -> int:
+        return len(self.trees)
+
+    def __getstate__(self):
+        # the flattened tables and the torch module are caches: a pickled
+        # predictor carries the trees alone and rebuilds them on demand
+        state = dict(self.__dict__)
+        state["_flat"] = None
+        state["_module"] = None
+        return state
+
+    # ------------------------------------------------------------------ #
+
+    def _flatten(self):
+        """Concatenated node tables with absolute child indices (leaves loop
+        onto themselves), the per-tree roots and the maximum depth."""
+        if self._flat is None:
+            feats, thrs, lefts, rights, vals, roots = [], [], [], [], [], []
+            off, depth = 0, 0
+            for ti, tr in enumerate(self.trees):
+                nn_ = tr["feature"].shape[0]
+                internal = tr["left"] >= 0
+                own = np.arange(nn_) + off
+                feats.append(tr["feature"])
+                thrs.append(np.where(internal, tr["threshold"], 0.0))
+                lefts.append(np.where(internal, tr["left"] + off, own))
+                rights.append(np.where(internal, tr["right"] + off, own))
+                v = tr["value"]
+                if not self.vector_leaves:
+                    full = np.zeros((nn_, self._n_out))
+                    full[:, self.out_col[ti]] = v
+                    v = full
+                vals.append(np.where(internal[:, None], 0.0, v))
+                roots.append(off)
+                # depth by one pass down from the root
+                d = np.zeros(nn_, dtype=np.int64)
+                stack = [0]
+                while stack:
+                    i = stack.pop()
+                    if internal[i]:
+                        for c in (tr["left"][i], tr["right"][i]):
+                            d[c] = d[i] + 1
+                            stack.append(int(c))
+                depth = max(depth, int(d.max()))
+                off += nn_
+            self._flat = {
+                "feature": np.concatenate(feats), "threshold": np.concatenate(thrs),
+                "left": np.concatenate(lefts), "right": np.concatenate(rights),
+                "value": np.concatenate(vals), "roots": np.asarray(roots),
+                "depth": depth,
+            }
+        return self._flat
+
+    def raw(self, X: np.ndarray) -> np.ndarray:
+        """``base + scale · Σ_t leaf`` before the activation (fp64)."""
+        f = self._flatten()
+        X = np.asarray(X)
+        if X.ndim != 2 or X.shape[1] != self.n_features:
+            raise ValueError(f"X must be (n, {self.n_features})")
+        if np.isnan(X).any():
+            raise ValueError(
+                "TreeEnsemblePredictor does not support NaN inputs (sklearn "
+                "routes missing values per node; these tables do not)")
+        # sklearn's rule: round the input to float32, compare in float64
+        x32 = X.astype(np.float32).astype(np.float64)
+        out = np.empty((X.shape[0], self._n_out))
+        step = max(1, (1 << 22) // self.n_trees)
+        for lo in range(0, X.shape[0], step):
+            xs = x32[lo : lo + step]
+            rows = np.arange(xs.shape[0])[:, None]
+            idx = np.broadcast_to(f["roots"][None, :], (xs.shape[0], self.n_trees))
+            for _ in range(f["depth"]):
+                go_left = xs[rows, f["feature"][idx]] <= f["threshold"][idx]
+                idx = np.where(go_left, f["left"][idx], f["right"][idx])
+            out[lo : lo + step] = self.base + self.scale * f["value"][idx].sum(axis=1)
+        return out
+
+    def __call__(self, X: np.ndarray) -> np.ndarray:
+        z = self.raw(X)
+        if self.activation == "softmax":
+            return _softmax(z)
+        if self.activation == "sigmoid":
+            return 1.0 / (1.0 + np.exp(-z))
+        return z
+
+    # protocol hook for the fused GPU path
+    def tree_params(self):
+        return {
+            "trees": self.trees, "n_features": self.n_features,
+            "n_out": self._n_out, "base": self.base, "scale": self.scale,
+            "out_col": self.out_col, "activation": self.activation,
+        }
+
+    def build_module(self, dtype=None):
+        """Gather-traversal ``nn.Module``: a node-index tensor steps
+        ``max_depth`` times. fp32 (default) compares float32 rows against
+        thresholds rounded down to float32, which equals the float64 rule
+        exactly; float64 rounds the rows to float32 and compares in float64."""
+        import torch
+
+        from .tree_module import TreeModule
+
+        dtype = dtype or torch.float32
+        return TreeModule(self._flatten(), self.base, self.scale,
+                          self.activation, dtype).eval()
+
+    def torch_module(self):
+        """fp32 module with the same tables (built once)."""
+        if self._module is None:
+            self._module = self.build_module()
+        return self._module
+
+    # ------------------------------------------------------------------ #
+
+    @classmethod
+    def random(cls, d: int, n_out: int = 2, trees: int = 100, depth: int = 4,
+               seed: int = 0, activation: str = "softmax",
+               vector_leaves: bool = False, p_stop: float = 0.2):
+        """Philox-seeded ensemble of non-complete trees: below the root a
+        branch ends early with probability ``p_stop``. Thresholds are drawn
+        for standard-normal features; leaves are scaled so that the raw score
+        has a standard deviation of about 1.5."""
+        rng = np.random.Generator(np.random.Philox(key=[seed, 0x7AEE5]))
+        per_col = max(1.0, trees if vector_leaves else trees / n_out)
+        sigma = 1.5 / np.sqrt(per_col)
+        out = []
+        for _ in range(trees):
+            feat, thr, left, right, val = [], [], [], [], []
+
+            def grow(level):
+                i = len(feat)
+                feat.append(-1), thr.append(0.0), left.append(-1), right.append(-1)
+                val.append(rng.normal(0.0, sigma, size=n_out) if vector_leaves
+                           else rng.normal(0.0, sigma))
+                if level < depth and (level == 0 or rng.uniform() >= p_stop):
+                    feat[i] = int(rng.integers(d))
+                    thr[i] = float(rng.normal())
+                    left[i] = grow(level + 1)
+                    right[i] = grow(level + 1)
+                return i
+
+            grow(0)
+            out.append({"feature": feat, "threshold": thr, "left": left,
+                        "right": right, "value": np.asarray(val)})
+        out_col = None if vector_leaves else np.arange(trees) % n_out
+        return cls(out, d, n_out, base=rng.normal(0.0, 0.1, size=n_out),
+                   scale=1.0, out_col=out_col, activation=activation)
+
+    @classmethod
+    def from_sklearn(cls, est):
+        """Wrap a fitted sklearn tree model: ``DecisionTree*``,
+        ``RandomForest*`` / ``ExtraTrees*``, ``GradientBoostingRegressor`` and
+        ``GradientBoostingClassifier(loss="log_loss")``. Raises ``TypeError``
+        with the reason for anything else. The wrapped model agrees with
+        the estimator on rows without NaN only (see the class docstring)."""
+        name = type(est).__name__
+        if not type(est).__module__.startswith("sklearn."):
+            raise TypeError(f"{name} is not a sklearn estimator")
+        if name.startswith("HistGradientBoosting"):
+            raise TypeError(
+                f"{name} is not supported: it compares in float64 on binned "
+                "data and routes missing values and categories separately")
+        from sklearn.ensemble import (ExtraTreesClassifier, ExtraTreesRegressor,
+                                      GradientBoostingClassifier,
+                                      GradientBoostingRegressor,
+                                      RandomForestClassifier,
+                                      RandomForestRegressor)
+        from sklearn.tree import DecisionTreeClassifier, DecisionTreeRegressor
+
+        if getattr(est, "n_outputs_", 1) != 1:
+            raise TypeError(
+                f"{name} was fitted on {est.n_outputs_} outputs; multi-output "
+                "estimators are not supported")
+
+        def table(tree, classes):
+            t = tree.tree_
+            v = t.value[:, 0, :]
+            if classes:
+                v = v / v.sum(axis=1, keepdims=True)
+            else:
+                v = v[:, 0]
+            return {"feature": t.feature, "threshold": t.threshold,
+                    "left": t.children_left, "right": t.children_right,
+                    "value": v}
+
+        d = int(est.n_features_in_)
+        if isinstance(est, (DecisionTreeClassifier, RandomForestClassifier,
+                            ExtraTreesClassifier)):
+            members = [est] if isinstance(est, DecisionTreeClassifier) \
+                else list(est.estimators_)
+            return cls([table(m, True) for m in members], d, len(est.classes_),
+                       scale=1.0 / len(members), activation="none")
+        if isinstance(est, (DecisionTreeRegressor, RandomForestRegressor,
+                            ExtraTreesRegressor)):
+            members = [est] if isinstance(est, DecisionTreeRegressor) \
+                else list(est.estimators_)
+            return cls([table(m, False) for m in members], d, 1,
+                       scale=1.0 / len(members), activation="none")
+        if isinstance(est, (GradientBoostingRegressor, GradientBoostingClassifier)):
+            stages = est.estimators_                      # (n_stages, K)
+            k = stages.shape[1]
+            if isinstance(est, GradientBoostingClassifier):
+                if est.loss != "log_loss":
+                    raise TypeError(
+                        f"GradientBoostingClassifier(loss={est.loss!r}) is not "
+                        "supported (only 'log_loss')")
+                n_out = len(est.classes_)
+                cols = [1 if k == 1 else j for _ in range(stages.shape[0])
+                        for j in range(k)]
+                act, score = "softmax", est.decision_function
+            else:
+                n_out, cols, act, score = 1, [0] * stages.shape[0], "none", est.predict
+            trees = [table(stages[i, j], False)
+                     for i in range(stages.shape[0]) for j in range(k)]
+            pred = cls(trees, d, n_out, scale=float(est.learning_rate),
+                       out_col=cols, activation=act)
+            # the constant init, from the public API only: the score minus
+            # our own tree sum, which must not depend on the row
+            rng = np.random.Generator(np.random.Philox(key=[0, 0xBA5E]))
+            probes = np.vstack([np.zeros(d), 10.0 * rng.normal(size=(2, d))])
+            sc = np.asarray(score(probes), dtype=np.float64).reshape(3, -1)
+            own = pred.raw(probes)
+            resid = sc - (own[:, 1:2] if (k == 1 and n_out == 2) else own)
+            if np.abs(resid - resid[0]).max() > 1e-9 * (1.0 + np.abs(sc).max()):
+                raise TypeError(
+                    f"{name} has a non-constant init estimator; only a "
+                    "constant initial score can be folded into the ensemble")
+            if k == 1 and n_out == 2:
+                pred.base = np.array([0.0, float(resid[0, 0])])
+            else:
+                pred.base = resid[0].copy()
+            return pred
+        raise TypeError(
+            f"{name} is not a supported tree model (DecisionTree*, "
+            "RandomForest*, ExtraTrees*, GradientBoostingRegressor, "
+            "GradientBoostingClassifier with log_loss)")
+
+
 def make_predictor(kind: str, d: int, n_out: int = 2, seed: int = 0, **kw):
     """Registry entry point used by benchmarks and serve config."""
     if kind == "linear":
         return LinearPredictor.random(d, n_out, seed)
+    if kind in ("trees", "trees_fused"):
+        pred = TreeEnsemblePredictor.random(
+            d, n_out, trees=kw.get("trees", 100), depth=kw.get("depth", 4),
+            seed=seed, activation=kw.get("activation", "softmax"),
+            vector_leaves=kw.get("vector_leaves", False),
+        )
+        if kind == "trees_fused":
+            return pred
+        # the same seeded ensemble behind the generic module path, so the
+        # two predict paths are directly comparable
+        return TorchPredictor(pred.build_module(), device=kw.get("device"))
     if kind == "mlp":
         import torch
         from torch import nn

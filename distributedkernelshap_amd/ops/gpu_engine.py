@@ -6,6 +6,7 @@ Per instance-bucket (instances sharing a varying-group pattern):
   fill_random_masks  (HIP K2, Philox)  ─┴─> masks (B,S,M) u8 on device
   fused_predict_linear (HIP K3-K6, MFMA)  -> ey (B,S,n_out)   [linear predictor]
      — or — fused_predict_mlp (HIP K4m, MFMA)  -> ey        [MLP predictor]
+     — or — fused_predict_trees (HIP K4t)      -> ey        [tree ensemble]
      — or — synth_chunk (HIP K3') + torch module + weighted mean  [torch predictor]
   link transform (torch, fp32)           -> eyAdj
   wls_solve (HIP K7)                     -> phi (B,M,n_out)
@@ -84,6 +85,8 @@ class GpuKernelShap:
         self.module = None
         self.mlp = None          # fp64 weights + operand images (MLPPredictor)
         self.mlp_fused = False   # True when fused_predict_mlp serves this engine
+        self.trees = None        # fp64 module + packed tables (TreeEnsemblePredictor)
+        self.trees_fused = False  # True when fused_predict_trees serves this engine
         lp = getattr(engine.predictor, "linear_params", None)
         if lp is not None:
             W, b, act = lp()
@@ -100,6 +103,8 @@ class GpuKernelShap:
             self.baseN = self.bg @ self.linear["W"].T + self.linear["b"]  # (N, o)
         elif getattr(engine.predictor, "mlp_params", None) is not None:
             self._init_mlp(engine.predictor)
+        elif getattr(engine.predictor, "tree_params", None) is not None:
+            self._init_trees(engine.predictor)
         else:
             tm = getattr(engine.predictor, "torch_module", None)
             if tm is not None:
@@ -278,10 +283,12 @@ class GpuKernelShap:
 
     def _ey_predict_nonlinear(self, masks, X_dev, varying):
         """ey for non-linear predictors, shared by the bucket loop and the
-        sample-sharded path: the fused MLP kernel when it applies, else the
-        synth + torch-module path."""
+        sample-sharded path: the fused tree or MLP kernel when it applies,
+        else the synth + torch-module path."""
         from . import mlp_pack
 
+        if self.trees_fused:
+            return self._ey_fused_trees(masks, X_dev, varying)
         if self.mlp_fused:
             if len(varying) <= mlp_pack.MAX_GROUPS:
                 return self._ey_fused_mlp(masks, X_dev, varying)
@@ -321,6 +328,114 @@ class GpuKernelShap:
         return ey
 
     # ------------------------------------------------------------------ #
+    # TreeEnsemblePredictor: fused_predict_trees (K4t) with the gather
+    # traversal torch module as the out-of-envelope fallback
+
+    def _init_trees(self, predictor):
+        from . import tree_pack
+
+        t = self.torch
+        kc = self.engine.kernels
+        if kc.predict_dtype not in ("fp32", "fp64"):
+            raise ValueError(
+                f"predict_dtype={kc.predict_dtype!r} is not available for "
+                "TreeEnsemblePredictor (a tree has nothing to round); "
+                "supported: 'fp32' (fused tree kernel) and 'fp64' "
+                "(verification)"
+            )
+        if kc.module_autocast == "bf16":
+            raise ValueError(
+                "module_autocast='bf16' is not available for "
+                "TreeEnsemblePredictor: features rounded to bf16 would flip "
+                "split decisions on the torch-module path"
+            )
+        params = predictor.tree_params()
+        # fp64 tables on the device: per-instance totals and verification
+        self.trees = {
+            "mod64": predictor.build_module(t.float64).to(self.device),
+            "act": params["activation"],
+        }
+        # every module-path consumer (fallback, sample-sharded) keeps
+        # working; a fresh module, so the caller's predictor is not touched
+        self.module = predictor.build_module().to(self.device)
+        if kc.predict_dtype == "fp64":
+            eng = self.engine
+            self.trees["bg64"] = t.tensor(
+                eng.background, dtype=t.float64, device=self.device)
+            self.trees["wbg64"] = t.tensor(
+                eng.bg_weights, dtype=t.float64, device=self.device)
+            self.trees["fnull64"] = t.tensor(
+                eng.fnull, dtype=t.float64, device=self.device)
+            return
+        reason = (None if kc.fused_predict
+                  else "kernels.fused_predict is off")
+        reason = reason or tree_pack.envelope_reason(params)
+        if reason is not None:
+            # fit time only, so the reason is logged once per engine
+            logger.info(
+                "TreeEnsemblePredictor runs on the torch-module path, "
+                "not the fused tree kernel: %s", reason,
+            )
+            return
+        pack = tree_pack.pack_trees(params, self.engine._col_group, self.device)
+        self.trees["pack"] = pack
+        # fit-time constant shared by all instances: the background rows'
+        # split decisions, one u64 per (row, tree)
+        self.trees["dbg"] = tree_pack.decision_bits(pack, self.bg)
+        self.trees_fused = True
+
+    def _ey_fused_trees(self, masks, X_dev, varying):
+        """K4t: fused tree predict. Only ey (B,S,n_out) reaches HBM; the
+        per-call operands are the instances' packed decisions dx (B,T) and
+        the group -> varying-index table."""
+        from . import tree_pack
+
+        t = self.torch
+        b, s, m = masks.shape
+        pack = self.trees["pack"]
+        vmap_h = np.full(self.n_groups, -1, dtype=np.int32)
+        vmap_h[np.asarray(varying)] = np.arange(m, dtype=np.int32)
+        vmap = t.tensor(vmap_h, device=self.device)
+        dx = tree_pack.decision_bits(pack, X_dev)
+        ey = self._buf("ey", (b, s, self.n_out))
+        return tree_pack.fused_predict(
+            self.ext, pack, masks.contiguous(), vmap, dx, self.trees["dbg"],
+            self.bg_w, ey,
+        )
+
+    def _ey_trees_f64(self, masks, X_dev, varying, budget_bytes=256 << 20):
+        """fp64 verification path for TreeEnsemblePredictor
+        (predict_dtype='fp64'): explicit masked blend + fp64 gather
+        traversal on the SAME device masks, chunked like ``_ey_mlp_f64``."""
+        t = self.torch
+        b, s, m = masks.shape
+        vmap = np.full(self.n_groups, m, dtype=np.int64)
+        for i, g in enumerate(varying):
+            vmap[g] = i
+        colk = t.tensor(vmap[self.engine._col_group], device=self.device)
+        bg = self.trees["bg64"]
+        X64 = X_dev.double()
+        wbg64 = self.trees["wbg64"]
+        n_trees = self.trees["mod64"].roots.shape[0]
+        width = max(self.D, 4 * n_trees)
+        s_chunk = max(1, budget_bytes // (8 * 3 * b * self.N * width))
+        ey = t.empty(b, s, self.n_out, dtype=t.float64, device=self.device)
+        zero_col = t.zeros(b, 1, 1, dtype=t.bool, device=self.device)
+        for lo in range(0, s, s_chunk):
+            hi = min(lo + s_chunk, s)
+            mk = masks[:, lo:hi].bool()
+            # non-varying columns map to an always-off sentinel column m
+            mk = t.cat([mk, zero_col.expand(b, hi - lo, 1)], dim=2)[:, :, colk]
+            rows = t.where(
+                mk[:, :, None, :], X64[:, None, None, :], bg[None, None, :, :]
+            )                                             # (b, sc, N, D)
+            with t.no_grad():
+                p = self.trees["mod64"](rows.reshape(-1, self.D))
+            p = p.view(b, hi - lo, self.N, self.n_out)
+            ey[:, lo:hi] = t.einsum("bsno,n->bso", p, wbg64)
+        return ey
+
+    # ------------------------------------------------------------------ #
 
     def _link(self, p):
         t = self.torch
@@ -345,6 +460,9 @@ class GpuKernelShap:
             return z
         if self.mlp is not None:
             return self._mlp_forward_f64(rows.double())
+        if self.trees is not None:
+            with t.no_grad():
+                return self.trees["mod64"](rows)
         with t.no_grad():
             return self.module(rows).double()
 
@@ -827,6 +945,9 @@ class GpuKernelShap:
             # and H1pad x G result) + the xp1 operand image (H1pad x Mpad)
             h1 = self.mlp["pack"]["hpad"][0]
             per_inst += 8 * g * (self.D + 2 * h1) + 4 * h1 * (g + 31)
+        if self.trees_fused:
+            # packed decisions dx plus the (T, 64) comparison image behind them
+            per_inst += self.trees["pack"]["n_trees"] * (8 + 64 * 9)
         return max(1, self._CHUNK_BYTES // per_inst)
 
     def shap_values(
@@ -888,16 +1009,17 @@ class GpuKernelShap:
 
         fp64 = self.engine.kernels.predict_dtype == "fp64"
         X64_dev = None
-        if fp64 and self.mlp is not None:
-            # MLP verification mode: inputs stay fp64 end to end (the fp32
-            # rounding of x alone shifts phi by ~1e-7)
+        f64c = self.mlp if self.mlp is not None else self.trees
+        if fp64 and f64c is not None:
+            # MLP / tree verification mode: inputs stay fp64 end to end (the
+            # fp32 rounding of x alone shifts phi by ~1e-7)
             X64_dev = (X.to(self.device).double() if t.is_tensor(X)
                        else t.tensor(X, dtype=t.float64, device=self.device))
         fx = self._predict_rows_f64(                    # (B, n_out) fp64
             X_dev if X64_dev is None else X64_dev)
         lfx = self._link(fx)
         lfnull64 = self._link(
-            self.fnull.double() if X64_dev is None else self.mlp["fnull64"])
+            self.fnull.double() if X64_dev is None else f64c["fnull64"])
         total_all = (lfx - lfnull64[None, :])           # (B, n_out) fp64
         if not fp64:
             total_all = total_all.float()
@@ -1209,7 +1331,7 @@ class GpuKernelShap:
         device masks, exact fp64 kernel weights (rebuilt from the plan's
         fp64 arrays, not the fp32 device copy), fp64 link and WLS."""
         t = self.torch
-        if self.linear is None and self.mlp is None:
+        if self.linear is None and self.mlp is None and self.trees is None:
             raise TypeError(
                 "predict_dtype='fp64' is the linear-predictor verification "
                 "mode; torch-module predictors have no fp64 reference "
@@ -1218,6 +1340,8 @@ class GpuKernelShap:
         b = sub_X.shape[0]
         if self.mlp is not None:
             ey = self._ey_mlp_f64(masks, sub_X, varying)
+        elif self.trees is not None:
+            ey = self._ey_trees_f64(masks, sub_X, varying)
         else:
             ey = self._ey_linear_f64(masks, sub_X, varying)
         kw64 = t.from_numpy(

@@ -1,5 +1,5 @@
 // Torch bindings for the CDNA4 KernelSHAP kernels (kshap_kernels.hip,
-// mlp_kernels.hip).
+// mlp_kernels.hip, tree_kernels.hip).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <c10/hip/HIPStream.h>
@@ -76,6 +76,15 @@ extern "C" int launch_fused_predict_mlp(
     const float* wbg, float* ey, int B, int S, int M, int Mpad, int N,
     int n_out, int act, int hidden_act, int is_bf16, int nsplit,
     hipStream_t stream);
+
+// tree_kernels.hip
+extern "C" int launch_fused_predict_trees(
+    const uint8_t* masks, const int* vmap, const int64_t* dx, const int64_t* dbg,
+    const uint8_t* child, const int* meta, const float* leaves,
+    const int* grp_off, const int* grp_id, const int64_t* grp_mask,
+    const float* base, const float* wbg, float* ey, float scale,
+    int B, int S, int Mv, int N, int T, int G, int E, int L, int C,
+    int max_internal, int n_out, int act, int leaf_mode, hipStream_t stream);
 
 namespace {
 
@@ -397,9 +406,83 @@ void fused_predict_mlp(
     TORCH_CHECK(rc == 0, envelope);
 }
 
+void fused_predict_trees(
+    torch::Tensor masks, torch::Tensor vmap, torch::Tensor dx,
+    torch::Tensor dbg, torch::Tensor child, torch::Tensor meta,
+    torch::Tensor leaves, torch::Tensor grp_off, torch::Tensor grp_id,
+    torch::Tensor grp_mask, torch::Tensor base, double scale,
+    torch::Tensor wbg, torch::Tensor ey, int64_t act, int64_t leaf_mode,
+    int64_t max_internal) {
+    static const char* envelope =
+        "fused_predict_trees: outside the supported envelope (1-1024 trees of "
+        "at most 64 internal nodes each, n_out <= 8, 128 B per tree plus 2 B "
+        "per internal node within 160 KiB of LDS)";
+    CHECK_DEV(masks); CHECK_DEV(vmap); CHECK_DEV(dx); CHECK_DEV(dbg);
+    CHECK_DEV(child); CHECK_DEV(meta); CHECK_DEV(leaves); CHECK_DEV(grp_off);
+    CHECK_DEV(grp_id); CHECK_DEV(grp_mask); CHECK_DEV(base); CHECK_DEV(wbg);
+    CHECK_DEV(ey);
+    TORCH_CHECK(masks.dtype() == torch::kUInt8 && masks.dim() == 3,
+                "masks must be u8 (B,S,Mv)");
+    TORCH_CHECK(ey.dtype() == torch::kFloat32 && ey.dim() == 3,
+                "ey must be f32 (B,S,n_out)");
+    const int B = masks.size(0), S = masks.size(1), Mv = masks.size(2);
+    const int n_out = ey.size(2);
+    TORCH_CHECK(ey.size(0) == B && ey.size(1) == S, "ey must be f32 (B,S,n_out)");
+    TORCH_CHECK(vmap.dtype() == torch::kInt32 && vmap.dim() == 1,
+                "the group table must be int32 (G)");
+    TORCH_CHECK(dx.dtype() == torch::kInt64 && dx.dim() == 2 && dx.size(0) == B,
+                "dx must be int64 (B,T)");
+    const int T = dx.size(1);
+    TORCH_CHECK(dbg.dtype() == torch::kInt64 && dbg.dim() == 2
+                && dbg.size(1) == T, "dbg must be int64 (N,T)");
+    const int N = dbg.size(0);
+    TORCH_CHECK(child.dtype() == torch::kUInt8 && child.dim() == 2
+                && child.size(1) == 2, "child must be u8 (C,2)");
+    TORCH_CHECK(meta.dtype() == torch::kInt32 && meta.dim() == 2
+                && meta.size(0) == T && meta.size(1) == 4,
+                "meta must be int32 (T,4)");
+    TORCH_CHECK(leaf_mode == 0 || leaf_mode == 1, "leaf_mode must be 0 or 1");
+    TORCH_CHECK(leaves.dtype() == torch::kFloat32
+                && (leaf_mode == 0 ? leaves.dim() == 1
+                                   : (leaves.dim() == 2 && leaves.size(1) == n_out)),
+                "leaves must be f32 (L) for scalar or (L,n_out) for vector leaves");
+    TORCH_CHECK(grp_off.dtype() == torch::kInt32 && grp_off.dim() == 1
+                && grp_off.size(0) == T + 1, "grp_off must be int32 (T+1)");
+    TORCH_CHECK(grp_id.dtype() == torch::kInt32 && grp_id.dim() == 1,
+                "grp_id must be int32 (E)");
+    TORCH_CHECK(grp_mask.dtype() == torch::kInt64 && grp_mask.dim() == 1
+                && grp_mask.size(0) == grp_id.size(0), "grp_mask must be int64 (E)");
+    TORCH_CHECK(base.dtype() == torch::kFloat32 && base.numel() == n_out,
+                "base must be f32 (n_out)");
+    TORCH_CHECK(wbg.dtype() == torch::kFloat32 && wbg.numel() == N,
+                "wbg must be f32 (N)");
+    TORCH_CHECK(max_internal <= 64 && max_internal >= 1, envelope);
+    int rc = launch_fused_predict_trees(
+        masks.data_ptr<uint8_t>(), vmap.data_ptr<int>(), dx.data_ptr<int64_t>(),
+        dbg.data_ptr<int64_t>(), child.data_ptr<uint8_t>(), meta.data_ptr<int>(),
+        leaves.data_ptr<float>(), grp_off.data_ptr<int>(), grp_id.data_ptr<int>(),
+        grp_mask.data_ptr<int64_t>(), base.data_ptr<float>(),
+        wbg.data_ptr<float>(), ey.data_ptr<float>(), (float)scale, B, S, Mv, N,
+        T, (int)vmap.size(0), (int)grp_id.size(0), (int)leaves.size(0),
+        (int)child.size(0), (int)max_internal, n_out, (int)act, (int)leaf_mode,
+        current_stream());
+    TORCH_CHECK(rc != -2, "fused_predict_trees: LDS size attribute rejected");
+    TORCH_CHECK(rc == 0, envelope);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+    m.def("fused_predict_trees", &fused_predict_trees,
+          "fused tree-ensemble predict (K4t): per-tree node masks in LDS, "
+          "bitwise select of packed x / background decisions, bit-register walk",
+          pybind11::arg("masks"), pybind11::arg("vmap"), pybind11::arg("dx"),
+          pybind11::arg("dbg"), pybind11::arg("child"), pybind11::arg("meta"),
+          pybind11::arg("leaves"), pybind11::arg("grp_off"),
+          pybind11::arg("grp_id"), pybind11::arg("grp_mask"),
+          pybind11::arg("base"), pybind11::arg("scale"), pybind11::arg("wbg"),
+          pybind11::arg("ey"), pybind11::arg("act"), pybind11::arg("leaf_mode"),
+          pybind11::arg("max_internal"));
     m.def("fused_predict_mlp", &fused_predict_mlp,
           "fused MLP predict (K4m): first layer folded over varying groups, "
           "hidden activations in LDS, f32 or bf16 MFMA by operand dtype",

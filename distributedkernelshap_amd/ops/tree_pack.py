@@ -1,0 +1,192 @@
+"""Packed tables for the fused tree predict kernel (``fused_predict_trees``).
+
+Everything here is numpy on the host plus plain torch on small tensors: the
+tables are built once per engine, ``decision_bits`` runs once at fit for the
+background and once per call for the instances.
+
+Per-tree layout (matching ``ops/hip/tree_kernels.hip``):
+
+  internal nodes are renumbered 0..I-1 in preorder with the root at 0, I <= 64,
+  so one u64 holds all of a tree's split decisions (bit i = "node i goes left")
+
+  feat, thr   (T, Ipad) int64 / f64   split feature and threshold of node i;
+                                      pad slots compare against -inf (bit 0)
+  child       (C, 2) u8               child[off_t + i][bit]; bit 1 = left.
+                                      < 64: internal node; else 64 + leaf index
+                                      within the tree.  C is padded to a
+                                      multiple of 8 nodes
+  meta        (T, 4) int32            child offset, leaf offset, out col, I
+  leaves      (L,) or (L, n_out) f32  leaf values in tree order
+  grp_off     (T + 1) int32           CSR over each tree's coalition groups
+  grp_id      (E) int32               group id
+  grp_mask    (E) int64               u64 mask of the tree's nodes that split
+                                      on a feature of that group
+
+A tree that is a single leaf gets one dummy internal node whose children are
+both that leaf.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+MAX_NODES = 64        # internal nodes per tree
+MAX_NOUT = 8
+MAX_TREES = 1024
+LDS_BYTES = 160 * 1024
+_THREADS = 1024       # workgroup size of the kernel (reduction scratch)
+
+ACT_CODE = {"none": 0, "sigmoid": 1, "softmax": 2}
+
+
+def _internal_counts(trees):
+    return [max(1, int((np.asarray(tr["left"]) >= 0).sum())) for tr in trees]
+
+
+def _child_rows(counts) -> int:
+    return (sum(counts) + 7) // 8 * 8
+
+
+def lds_bytes_min(n_trees: int, child_rows: int, n_out: int) -> int:
+    """LDS the kernel needs at its narrowest tile (16 samples per workgroup):
+    8 B x 16 per tree for the node masks (at least the reduction scratch)
+    plus 2 B per internal node for the child table."""
+    no = 1 if n_out <= 1 else 2 if n_out <= 2 else 4 if n_out <= 4 else 8
+    return max(n_trees * 16 * 8, _THREADS * no * 4) + 2 * child_rows
+
+
+def envelope_reason(params: dict):
+    """None when the ensemble fits the fused kernel, else a one-line reason."""
+    trees = params["trees"]
+    counts = _internal_counts(trees)
+    worst = int(np.argmax(counts))
+    if counts[worst] > MAX_NODES:
+        return (f"tree {worst} has {counts[worst]} internal nodes "
+                f"(supported: <= {MAX_NODES})")
+    if params["n_out"] > MAX_NOUT:
+        return f"n_out {params['n_out']} (supported: <= {MAX_NOUT})"
+    if len(trees) > MAX_TREES:
+        return f"{len(trees)} trees (supported: <= {MAX_TREES})"
+    need = lds_bytes_min(len(trees), _child_rows(counts), params["n_out"])
+    if need > LDS_BYTES:
+        return (f"{len(trees)} trees with {sum(counts)} internal nodes need "
+                f"{need} B of LDS (supported: <= {LDS_BYTES})")
+    return None
+
+
+def pack_trees(params: dict, col_group, device) -> dict:
+    """Device tables for ``tree_params()`` output ``params`` and the
+    feature -> group map ``col_group`` (D,). No envelope check: the kernel
+    binding is the one place that refuses unsupported ensembles (a tree with
+    more than 64 internal nodes is packed with truncated codes and must not
+    be walked)."""
+    import torch as t
+
+    trees = params["trees"]
+    n_out = int(params["n_out"])
+    col_group = np.asarray(col_group, dtype=np.int64)
+    vector = params["out_col"] is None
+    counts = _internal_counts(trees)
+    ipad = max(MAX_NODES, max(counts))
+    n_trees = len(trees)
+    feat = np.zeros((n_trees, ipad), dtype=np.int64)
+    thr = np.full((n_trees, ipad), -np.inf)
+    child = np.zeros((_child_rows(counts), 2), dtype=np.int64)
+    meta = np.zeros((n_trees, 4), dtype=np.int32)
+    leaves, grp_off, grp_id, grp_mask = [], [0], [], []
+    coff = loff = 0
+    for ti, tr in enumerate(trees):
+        left = np.asarray(tr["left"])
+        right = np.asarray(tr["right"])
+        value = np.asarray(tr["value"], dtype=np.float64)
+        internal = left >= 0
+        # preorder renumbering of internal nodes and of leaves
+        code = np.zeros(left.shape[0], dtype=np.int64)
+        n_int = n_leaf = 0
+        order, stack = [], [0]
+        while stack:
+            i = stack.pop()
+            if internal[i]:
+                code[i] = n_int
+                n_int += 1
+                order.append(i)
+                stack.append(int(right[i]))
+                stack.append(int(left[i]))
+            else:
+                code[i] = MAX_NODES + n_leaf
+                n_leaf += 1
+                leaves.append(value[i])
+        if n_int == 0:
+            # single leaf: a dummy split on feature 0 whose sides agree
+            child[coff] = MAX_NODES
+            n_int = 1
+        else:
+            for i in order:
+                k = code[i]
+                feat[ti, k] = tr["feature"][i]
+                thr[ti, k] = tr["threshold"][i]
+                child[coff + k, 1] = code[left[i]]
+                child[coff + k, 0] = code[right[i]]
+            by_group: dict = {}
+            for i in order:
+                g = int(col_group[tr["feature"][i]])
+                by_group[g] = by_group.get(g, 0) | (1 << int(code[i] % 64))
+            for g in sorted(by_group):
+                grp_id.append(g)
+                grp_mask.append(by_group[g])
+        grp_off.append(len(grp_id))
+        meta[ti] = (coff, loff, 0 if vector else int(params["out_col"][ti]), n_int)
+        coff += n_int
+        loff += n_leaf
+    leaves = np.asarray(leaves, dtype=np.float32)
+    if not grp_id:                       # every tree is a single leaf
+        grp_id, grp_mask = [0], [0]
+    gm = np.asarray(grp_mask, dtype=np.uint64).view(np.int64)
+
+    def dev(a):
+        return t.from_numpy(np.ascontiguousarray(a)).to(device)
+
+    return {
+        "n_trees": n_trees, "n_out": n_out, "leaf_mode": 1 if vector else 0,
+        "max_internal": int(max(counts)),
+        "feat": dev(feat), "thr": dev(thr),
+        "child": dev(np.minimum(child, 255).astype(np.uint8)),
+        "meta": dev(meta), "leaves": dev(leaves),
+        "grp_off": dev(np.asarray(grp_off, dtype=np.int32)),
+        "grp_id": dev(np.asarray(grp_id, dtype=np.int32)),
+        "grp_mask": dev(gm),
+        "base": dev(np.asarray(params["base"], dtype=np.float32)),
+        "scale": float(params["scale"]),
+        "act": ACT_CODE[params["activation"]],
+    }
+
+
+def decision_bits(pack: dict, rows):
+    """(R, T) int64: bit i of [r, t] is ``float64(float32(rows[r, feat_i]))
+    <= thr_i`` for internal node i of tree t — sklearn's comparison rule,
+    evaluated in torch on the device of ``rows``."""
+    import torch as t
+
+    feat, thr = pack["feat"], pack["thr"]
+    n_trees, ipad = feat.shape
+    x = rows.float().double()
+    shifts = t.arange(ipad, device=x.device, dtype=t.int64) % 64
+    out = t.empty(x.shape[0], n_trees, dtype=t.int64, device=x.device)
+    step = max(1, (1 << 24) // (n_trees * ipad))
+    flat = feat.reshape(-1)
+    for lo in range(0, x.shape[0], step):
+        xs = x[lo : lo + step]
+        go_left = xs[:, flat].view(-1, n_trees, ipad) <= thr[None]
+        # disjoint bits: the wrapping int64 sum is the OR, bit 63 included
+        out[lo : lo + step] = (go_left.to(t.int64) << shifts).sum(dim=-1)
+    return out
+
+
+def fused_predict(ext, pack: dict, masks, vmap, dx, dbg, wbg, ey):
+    """Launch ``fused_predict_trees`` with the packed tables."""
+    ext.fused_predict_trees(
+        masks, vmap, dx, dbg, pack["child"], pack["meta"], pack["leaves"],
+        pack["grp_off"], pack["grp_id"], pack["grp_mask"], pack["base"],
+        pack["scale"], wbg, ey, pack["act"], pack["leaf_mode"],
+        pack["max_internal"],
+    )
+    return ey

@@ -159,8 +159,9 @@ def _wrap_sklearn_mlp(obj):
 def load_model(path: str = None):
     """Unpickle a predictor; sklearn LogisticRegression is wrapped into the
     native LinearPredictor and sklearn MLPClassifier / MLPRegressor into
-    the native MLPPredictor, so the fused GPU paths apply
-    (reference ``load_model``, utils.py:137-157)."""
+    the native MLPPredictor, and sklearn decision trees, forests and
+    gradient boosting into the native TreeEnsemblePredictor, so the fused
+    GPU paths apply (reference ``load_model``, utils.py:137-157)."""
     import pickle
 
     path = path or os.path.join(ASSETS_DIR, "predictor.pkl")
@@ -182,6 +183,12 @@ def load_model(path: str = None):
     coefs = getattr(obj, "coefs_", None)
     if coefs is not None and hasattr(obj, "out_activation_"):
         return _wrap_sklearn_mlp(obj)
+    if type(obj).__module__.startswith(("sklearn.tree", "sklearn.ensemble")) \
+            and (hasattr(obj, "tree_") or hasattr(obj, "estimators_")):
+        # raises TypeError with the reason for an unsupported tree model
+        from ..models.predictors import TreeEnsemblePredictor
+
+        return TreeEnsemblePredictor.from_sklearn(obj)
     if not callable(obj):
         raise TypeError(f"loaded object {type(obj)} is not a predictor")
     return obj
