@@ -1,0 +1,171 @@
+"""Fused kernel-machine predict kernel vs the torch-module path, same run, same
+machine.
+
+Default shape: 256 instances, 100 background rows, 64 features (64 singleton
+groups), an rbf machine with 512 support vectors, n_out = 2, softmax, default
+sample count, ``l1_reg=False``. Paths:
+
+  module   make_predictor("svm")        GEMM-form module on synth rows
+  fused    make_predictor("svm_fused")  fused_predict_kernelmachine
+  cpu      make_predictor("svm_fused")  CPU engine on ``--cpu-instances`` rows
+
+Each path runs in a child process of its own under a time limit; the driver
+stops at the first child that fails. Every step is timed by a host clock
+around work that ends in a device synchronise; after ``--warmup`` steps the
+median and the spread of ``--steps`` timed steps are reported. The fused path
+also prints ``max_phi_err_vs_fp64`` (the first ``--selfcheck`` instances
+re-explained in the fp64 device mode on identical coalition masks); both GPU
+paths print a per-stage trace.
+
+    python benchmarks/km_fused.py                 # all three paths
+    python benchmarks/km_fused.py --path fused
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+PATHS = {
+    # name: (predictor kind, device)
+    "module": ("svm", "cuda"),
+    "fused": ("svm_fused", "cuda"),
+    "cpu": ("svm_fused", "cpu"),
+}
+
+
+def run_path(args) -> dict:
+    import numpy as np
+    import torch
+
+    from distributedkernelshap_amd.config import KernelConfig
+    from distributedkernelshap_amd.core.engine import KernelShapEngine
+    from distributedkernelshap_amd.models import make_predictor, make_tabular
+
+    if not torch.cuda.is_available():
+        raise SystemExit("km_fused.py measures on a GPU; none is visible")
+    kind, device = PATHS[args.path]
+    instances = args.cpu_instances if device == "cpu" else args.instances
+    data = make_tabular(
+        n_features=64, n_instances=args.instances,
+        n_background=args.background, seed=1000,
+    )
+    pred = make_predictor(kind, 64, 2, seed=0, n_sv=args.n_sv,
+                          kernel=args.kernel, degree=args.degree,
+                          coef0=args.coef0)
+    engine = KernelShapEngine(
+        pred, data.background, groups=data.groups, link="logit", seed=0,
+        device=device,
+    )
+    X_np = data.X[:instances]
+    X_in = torch.from_numpy(X_np.astype(np.float32)) if device == "cuda" else X_np
+
+    def step():
+        out = engine.shap_values(X=X_in, l1_reg=False)
+        if device == "cuda":
+            torch.cuda.synchronize()
+        return out
+
+    warmup, steps = (0, 1) if device == "cpu" else (args.warmup, args.steps)
+    for _ in range(warmup):
+        step()
+    times = []
+    for _ in range(steps):
+        t0 = time.perf_counter()
+        out = step()
+        times.append(time.perf_counter() - t0)
+    med = statistics.median(times)
+    res = {
+        "path": args.path,
+        "instances": instances,
+        "n_sv": args.n_sv,
+        "kernel": args.kernel,
+        "steps": steps,
+        "warmup": warmup,
+        "expl_per_s_median": instances / med,
+        "expl_per_s_min": instances / max(times),
+        "expl_per_s_max": instances / min(times),
+        "ms_per_step_median": med * 1e3,
+        "ms_per_step_all": [round(t * 1e3, 3) for t in times],
+    }
+    if device == "cpu":
+        return res
+    res["km_fused"] = bool(getattr(engine._gpu, "km_fused", False))
+    if kind == "svm_fused":
+        assert res["km_fused"], "fused path expected but not taken"
+        k = min(args.selfcheck, instances)
+        eng64 = KernelShapEngine(
+            pred, data.background, groups=data.groups, link="logit", seed=0,
+            device="cuda", kernels=KernelConfig(predict_dtype="fp64"),
+        )
+        sv64 = eng64.shap_values(data.X[:k], l1_reg=False)
+        sv = engine.shap_values(data.X[:k], l1_reg=False)
+        res["max_phi_err_vs_fp64"] = float(
+            max(np.abs(sv[o] - sv64[o]).max() for o in range(len(sv64)))
+        )
+        res["max_abs_phi_fp64"] = float(max(np.abs(s).max() for s in sv64))
+    del out
+    engine.enable_tracing(True)
+    step()
+    res["trace_ms"] = {
+        name: round(sum(v), 3) for name, v in engine.get_trace().items()
+    }
+    return res
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--path", choices=sorted(PATHS), default=None,
+                    help="run one path in this process (default: all three, "
+                         "each in a child process under --timeout)")
+    ap.add_argument("--instances", type=int, default=256)
+    ap.add_argument("--background", type=int, default=100)
+    ap.add_argument("--n-sv", type=int, default=512)
+    ap.add_argument("--kernel", choices=["rbf", "poly"], default="rbf")
+    ap.add_argument("--degree", type=int, default=3)
+    ap.add_argument("--coef0", type=float, default=0.0)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--selfcheck", type=int, default=8,
+                    help="instances re-explained in fp64 for the error figure")
+    ap.add_argument("--cpu-instances", type=int, default=1,
+                    help="instances the CPU engine explains, once, for scale")
+    ap.add_argument("--timeout", type=float, default=240.0,
+                    help="seconds per child process")
+    args = ap.parse_args()
+    if args.steps < 5:
+        ap.error("--steps must be at least 5 (median and spread)")
+
+    if args.path is not None:
+        print(json.dumps(run_path(args)), flush=True)
+        return
+
+    passthrough = [
+        "--instances", str(args.instances), "--background", str(args.background),
+        "--n-sv", str(args.n_sv), "--kernel", args.kernel,
+        "--degree", str(args.degree), "--coef0", str(args.coef0),
+        "--steps", str(args.steps), "--warmup", str(args.warmup),
+        "--selfcheck", str(args.selfcheck),
+        "--cpu-instances", str(args.cpu_instances),
+    ]
+    for name in ("module", "fused", "cpu"):
+        cmd = [sys.executable, os.path.abspath(__file__), "--path", name]
+        try:
+            proc = subprocess.run(cmd + passthrough, timeout=args.timeout)
+        except subprocess.TimeoutExpired:
+            raise SystemExit(f"{name}: no result within {args.timeout:.0f} s; "
+                             "stopping")
+        if proc.returncode != 0:
+            raise SystemExit(f"{name}: exit status {proc.returncode}; stopping")
+
+
+if __name__ == "__main__":
+    main()

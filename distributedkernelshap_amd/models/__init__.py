@@ -1,4 +1,5 @@
 from .predictors import (  # noqa: F401
+    KernelMachinePredictor,
     LinearPredictor,
     MLPPredictor,
     TorchPredictor,

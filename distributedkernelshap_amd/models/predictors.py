@@ -15,6 +15,12 @@ Here predictors are first-class objects:
   forests) with explicit node tables; exposes ``tree_params()`` so the GPU
   engine can run the fused tree HIP kernel (split decisions packed to bits
   once per row, a bitwise select and a bit-register walk per sample).
+* ``KernelMachinePredictor`` — kernel SVM / kernel ridge (rbf or polynomial
+  kernel) with explicit support vectors and dual coefficients; exposes
+  ``kernel_machine_params()`` so the GPU engine can run the fused
+  kernel-machine HIP kernel (squared distance / dot product folded over
+  coalition groups, support vectors streamed in tiles, kernel evaluation and
+  the contraction with the dual coefficients on chip).
 * ``TorchPredictor`` — wraps any torch ``nn.Module`` (MLP / ResNet configs);
   the GPU engine materialises synth tiles on-device and calls the module
   stream-ordered.
@@ -25,8 +31,8 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["LinearPredictor", "MLPPredictor", "TorchPredictor",
-           "TreeEnsemblePredictor", "make_predictor"]
+__all__ = ["KernelMachinePredictor", "LinearPredictor", "MLPPredictor",
+           "TorchPredictor", "TreeEnsemblePredictor", "make_predictor"]
 
 
 def _softmax(z: np.ndarray) -> np.ndarray:
@@ -599,10 +605,291 @@ class TreeEnsemblePredictor:
             "GradientBoostingClassifier with log_loss)")
 
 
+class KernelMachinePredictor:
+    """Kernel machine with explicit parameters:
+    ``act(intercept + alpha · k(x, support_vectors))`` with
+
+    * ``kernel="rbf"``:  ``k(x, v) = exp(−gamma · |x − v|²)``
+    * ``kernel="poly"``: ``k(x, v) = (gamma · x·v + coef0) ** degree``
+
+    ``support_vectors`` is ``(V, D)``, ``alpha`` ``(n_out, V)`` (dual
+    coefficients), ``intercept`` ``(n_out,)``. This covers a binary
+    ``SVC`` / ``NuSVC`` decision function, ``SVR`` / ``NuSVR`` and
+    ``KernelRidge`` (see ``from_sklearn``).
+
+    ``__call__`` is the fp64 numpy oracle (rbf by the explicit difference,
+    chunked over rows); ``kernel_machine_params()`` is the protocol hook the
+    GPU engine uses to run the fused ``fused_predict_kernelmachine`` HIP
+    kernel; ``torch_module()`` is the fp32 ``nn.Module`` used when the
+    machine is outside that kernel's envelope.
+    """
+
+    _OUT = ("softmax", "sigmoid", "none")
+    _KERNELS = ("rbf", "poly")
+
+    def __init__(self, support_vectors, alpha, intercept, kernel: str = "rbf",
+                 gamma: float = 1.0, coef0: float = 0.0, degree: int = 3,
+                 activation: str = "none"):
+        if kernel not in self._KERNELS:
+            raise ValueError(f"unknown kernel {kernel!r} (supported: rbf, poly)")
+        if activation not in self._OUT:
+            raise ValueError(f"unknown activation {activation}")
+        sv = np.asarray(support_vectors, dtype=np.float64)
+        if sv.ndim != 2 or sv.shape[0] < 1 or sv.shape[1] < 1:
+            raise ValueError("support_vectors must be (V, D) with V, D >= 1")
+        al = np.asarray(alpha, dtype=np.float64)
+        if al.ndim != 2 or al.shape[0] < 1 or al.shape[1] != sv.shape[0]:
+            raise ValueError("alpha must be (n_out, V)")
+        ic = np.asarray(intercept, dtype=np.float64).reshape(-1)
+        if ic.shape[0] != al.shape[0]:
+            raise ValueError("intercept must have n_out entries")
+        gamma, coef0 = float(gamma), float(coef0)
+        if not np.isfinite(gamma) or gamma <= 0.0:
+            raise ValueError("gamma must be positive and finite")
+        if not np.isfinite(coef0):
+            raise ValueError("coef0 must be finite")
+        if isinstance(degree, bool) or float(degree) != int(degree) \
+                or int(degree) < 1:
+            raise ValueError("degree must be an integer >= 1")
+        if not (np.isfinite(sv).all() and np.isfinite(al).all()
+                and np.isfinite(ic).all()):
+            raise ValueError(
+                "support_vectors, alpha and intercept must be finite")
+        self.support_vectors = sv
+        self.alpha = al
+        self.intercept = ic
+        self.kernel = kernel
+        self.gamma = gamma
+        self.coef0 = coef0
+        self.degree = int(degree)
+        self.activation = activation
+        self._module = None
+
+    @property
+    def n_out(self) -> int:
+        return self.alpha.shape[0]
+
+    @property
+    def n_features(self) -> int:
+        return self.support_vectors.shape[1]
+
+    @property
+    def n_sv(self) -> int:
+        return self.support_vectors.shape[0]
+
+    def __getstate__(self):
+        # the torch module is a cache: a pickled predictor carries the
+        # parameters alone and rebuilds it on demand
+        state = dict(self.__dict__)
+        state["_module"] = None
+        return state
+
+    def kernel_values(self, X: np.ndarray) -> np.ndarray:
+        """``k(x, sv)`` for every row and support vector, ``(n, V)`` fp64."""
+        X = np.asarray(X, dtype=np.float64)
+        if self.kernel == "rbf":
+            diff = X[:, None, :] - self.support_vectors[None, :, :]
+            return np.exp(-self.gamma * (diff * diff).sum(axis=2))
+        return (self.gamma * (X @ self.support_vectors.T)
+                + self.coef0) ** self.degree
+
+    def raw(self, X: np.ndarray) -> np.ndarray:
+        """``intercept + alpha · k(x, sv)`` before the activation (fp64)."""
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[1] != self.n_features:
+            raise ValueError(f"X must be (n, {self.n_features})")
+        out = np.empty((X.shape[0], self.n_out))
+        # the rbf difference tensor is (rows, V, D): bound it, not (rows, V)
+        step = max(1, (1 << 22) // (self.n_sv * self.n_features))
+        for lo in range(0, X.shape[0], step):
+            k = self.kernel_values(X[lo : lo + step])
+            out[lo : lo + step] = k @ self.alpha.T + self.intercept
+        return out
+
+    def __call__(self, X: np.ndarray) -> np.ndarray:
+        z = self.raw(X)
+        if self.activation == "softmax":
+            return _softmax(z)
+        if self.activation == "sigmoid":
+            return 1.0 / (1.0 + np.exp(-z))
+        return z
+
+    # protocol hook for the fused GPU path
+    def kernel_machine_params(self):
+        return {
+            "support_vectors": self.support_vectors, "alpha": self.alpha,
+            "intercept": self.intercept, "kernel": self.kernel,
+            "gamma": self.gamma, "coef0": self.coef0, "degree": self.degree,
+            "activation": self.activation,
+        }
+
+    def build_module(self, dtype=None):
+        """GEMM-form ``nn.Module`` with the same parameters, fp32 (default)
+        or float64 (verification)."""
+        import torch
+
+        from .km_module import KernelMachineModule
+
+        dtype = dtype or torch.float32
+        return KernelMachineModule(
+            self.support_vectors, self.alpha, self.intercept, self.kernel,
+            self.gamma, self.coef0, self.degree, self.activation, dtype).eval()
+
+    def torch_module(self):
+        """fp32 module with the same parameters (built once)."""
+        if self._module is None:
+            self._module = self.build_module()
+        return self._module
+
+    # ------------------------------------------------------------------ #
+
+    @classmethod
+    def random(cls, d: int, n_out: int = 2, n_sv: int = 256,
+               kernel: str = "rbf", seed: int = 0, activation: str = "softmax",
+               coef0: float = 0.0, degree: int = 3):
+        """Philox-seeded machine: standard-normal support vectors,
+        ``gamma = 1/d``, dual coefficients scaled so that
+        ``Σ_v |alpha[o, v]| = 4`` for every output (kernel values of an rbf
+        machine lie in (0, 1], so the raw score stays within ±4 of the
+        intercept)."""
+        rng = np.random.Generator(np.random.Philox(key=[seed, 0x5F3A]))
+        sv = rng.normal(size=(n_sv, d))
+        alpha = rng.normal(size=(n_out, n_sv))
+        alpha *= 4.0 / np.abs(alpha).sum(axis=1, keepdims=True)
+        intercept = rng.normal(0.0, 0.1, size=n_out)
+        return cls(sv, alpha, intercept, kernel=kernel, gamma=1.0 / d,
+                   coef0=coef0, degree=degree, activation=activation)
+
+    @classmethod
+    def from_sklearn(cls, est, output: str = "decision"):
+        """Wrap a fitted sklearn kernel machine with an rbf or polynomial
+        kernel: a binary ``SVC`` / ``NuSVC`` (``n_out = 1``, equal to
+        ``decision_function``), ``SVR`` / ``NuSVR`` and ``KernelRidge`` with
+        up to 8 targets (equal to ``predict``). Raises ``TypeError`` with the
+        reason for anything else. What was read from the estimator is
+        checked against its public ``decision_function`` / ``predict`` on a
+        few probe rows.
+
+        ``output="proba"`` (``SVC(probability=True)`` only) gives
+        ``n_out = 2``: the softmax over ``[0, −(probA·f − probB)]`` with ``f``
+        the decision value, i.e. the closed-form Platt sigmoid
+        ``P(classes_[1]) = 1 / (1 + exp(probA·f − probB))``. libsvm's own
+        ``predict_proba`` runs an iterative pairwise coupling with a loose
+        stopping tolerance even for two classes and differs from the closed
+        form by about 3e-3; the probe check for this output is accordingly
+        loose (2e-2) and only guards the sign convention."""
+        if output not in ("decision", "proba"):
+            raise ValueError(f"unknown output {output!r} (decision, proba)")
+        name = type(est).__name__
+        if not type(est).__module__.startswith("sklearn."):
+            raise TypeError(f"{name} is not a sklearn estimator")
+        svm_names = ("SVC", "NuSVC", "SVR", "NuSVR")
+        if name not in svm_names + ("KernelRidge",):
+            raise TypeError(
+                f"{name} is not a supported kernel machine (SVC, NuSVC, SVR, "
+                "NuSVR, KernelRidge)")
+        kern = est.kernel
+        if callable(kern):
+            raise TypeError(f"{name} with a callable kernel is not supported")
+        if kern == "linear":
+            raise TypeError(
+                f"{name}(kernel='linear') is a linear model: use "
+                "LinearPredictor with its coef_ / intercept_")
+        if kern in ("poly", "polynomial"):
+            kern = "poly"
+        elif kern != "rbf":
+            raise TypeError(
+                f"{name}(kernel={kern!r}) is not supported (rbf, poly)")
+
+        def dense(a):
+            return np.asarray(a.toarray() if hasattr(a, "toarray") else a,
+                              dtype=np.float64)
+
+        if name == "KernelRidge":
+            sv = dense(est.X_fit_)
+            alpha = dense(est.dual_coef_)
+            alpha = alpha[None, :] if alpha.ndim == 1 else alpha.T
+            if alpha.shape[0] > 8:
+                raise TypeError(
+                    f"KernelRidge with {alpha.shape[0]} targets is not "
+                    "supported (at most 8)")
+            intercept = np.zeros(alpha.shape[0])
+            gamma = 1.0 / sv.shape[1] if est.gamma is None else float(est.gamma)
+            score = est.predict
+        else:
+            if name in ("SVC", "NuSVC") and len(est.classes_) != 2:
+                raise TypeError(
+                    f"multi-class {name} ({len(est.classes_)} classes) is not "
+                    "supported: one-vs-one votes / pairwise coupling are not "
+                    "of the form alpha · k(x, sv)")
+            sv = dense(est.support_vectors_)
+            alpha = dense(est.dual_coef_).reshape(1, -1)
+            intercept = np.asarray(est.intercept_, dtype=np.float64).reshape(1)
+            gamma = float(est._gamma if isinstance(est.gamma, str)
+                          else est.gamma)
+            score = (est.decision_function if name in ("SVC", "NuSVC")
+                     else est.predict)
+        if output == "proba" and (
+                name not in ("SVC", "NuSVC")
+                or not getattr(est, "probability", False)
+                or np.size(getattr(est, "probA_", ())) != 1):
+            raise TypeError(
+                "output='proba' needs a binary SVC / NuSVC fitted with "
+                "probability=True")
+        degree = est.degree if kern == "poly" else 3
+        if kern == "poly" and (float(degree) != int(degree) or degree < 1):
+            raise TypeError(
+                f"{name} has degree {degree!r}; only integer degrees >= 1 "
+                "are supported")
+        coef0 = float(est.coef0) if kern == "poly" else 0.0
+        try:
+            pred = cls(sv, alpha, intercept, kernel=kern, gamma=gamma,
+                       coef0=coef0, degree=int(degree), activation="none")
+        except ValueError as e:
+            raise TypeError(f"{name} cannot be wrapped: {e}") from None
+        # verify what was read against the public API, on rows near a few
+        # support vectors (far-away rows would only see underflowed kernels)
+        rng = np.random.Generator(np.random.Philox(key=[0, 0x5EED]))
+        pick = rng.integers(sv.shape[0], size=4)
+        spread = sv.std(axis=0) + 1e-12
+        probes = sv[pick] + 0.5 * spread * rng.normal(size=(4, sv.shape[1]))
+        sc = np.asarray(score(probes), dtype=np.float64).reshape(4, -1)
+        own = pred.raw(probes)
+        if own.shape != sc.shape or \
+                np.abs(own - sc).max() > 1e-9 * (1.0 + np.abs(sc).max()):
+            raise TypeError(
+                f"{name}: the parameters read from the estimator do not "
+                "reproduce its decision_function / predict")
+        if output == "decision":
+            return pred
+        pa, pb = float(est.probA_[0]), float(est.probB_[0])
+        proba = cls(sv, np.vstack([np.zeros_like(alpha[0]), -pa * alpha[0]]),
+                    np.array([0.0, -pa * intercept[0] + pb]), kernel=kern,
+                    gamma=gamma, coef0=coef0, degree=int(degree),
+                    activation="softmax")
+        lib = np.asarray(est.predict_proba(probes), dtype=np.float64)
+        if np.abs(proba(probes) - lib).max() > 2e-2:
+            raise TypeError(
+                f"{name}: the closed-form Platt sigmoid does not reproduce "
+                "predict_proba (sign convention)")
+        return proba
+
+
 def make_predictor(kind: str, d: int, n_out: int = 2, seed: int = 0, **kw):
     """Registry entry point used by benchmarks and serve config."""
     if kind == "linear":
         return LinearPredictor.random(d, n_out, seed)
+    if kind in ("svm", "svm_fused"):
+        pred = KernelMachinePredictor.random(
+            d, n_out, n_sv=kw.get("n_sv", 256), kernel=kw.get("kernel", "rbf"),
+            seed=seed, activation=kw.get("activation", "softmax"),
+            coef0=kw.get("coef0", 0.0), degree=kw.get("degree", 3),
+        )
+        if kind == "svm_fused":
+            return pred
+        # the same seeded machine behind the generic module path, so the
+        # two predict paths are directly comparable
+        return TorchPredictor(pred.build_module(), device=kw.get("device"))
     if kind in ("trees", "trees_fused"):
         pred = TreeEnsemblePredictor.random(
             d, n_out, trees=kw.get("trees", 100), depth=kw.get("depth", 4),

@@ -7,6 +7,7 @@ Per instance-bucket (instances sharing a varying-group pattern):
   fused_predict_linear (HIP K3-K6, MFMA)  -> ey (B,S,n_out)   [linear predictor]
      — or — fused_predict_mlp (HIP K4m, MFMA)  -> ey        [MLP predictor]
      — or — fused_predict_trees (HIP K4t)      -> ey        [tree ensemble]
+     — or — fused_predict_kernelmachine (K4k)  -> ey        [SVM / kernel ridge]
      — or — synth_chunk (HIP K3') + torch module + weighted mean  [torch predictor]
   link transform (torch, fp32)           -> eyAdj
   wls_solve (HIP K7)                     -> phi (B,M,n_out)
@@ -87,6 +88,8 @@ class GpuKernelShap:
         self.mlp_fused = False   # True when fused_predict_mlp serves this engine
         self.trees = None        # fp64 module + packed tables (TreeEnsemblePredictor)
         self.trees_fused = False  # True when fused_predict_trees serves this engine
+        self.km = None           # fp64 module + operand images (KernelMachinePredictor)
+        self.km_fused = False    # True when fused_predict_kernelmachine serves this engine
         lp = getattr(engine.predictor, "linear_params", None)
         if lp is not None:
             W, b, act = lp()
@@ -105,6 +108,8 @@ class GpuKernelShap:
             self._init_mlp(engine.predictor)
         elif getattr(engine.predictor, "tree_params", None) is not None:
             self._init_trees(engine.predictor)
+        elif getattr(engine.predictor, "kernel_machine_params", None) is not None:
+            self._init_kernel_machine(engine.predictor)
         else:
             tm = getattr(engine.predictor, "torch_module", None)
             if tm is not None:
@@ -283,12 +288,19 @@ class GpuKernelShap:
 
     def _ey_predict_nonlinear(self, masks, X_dev, varying):
         """ey for non-linear predictors, shared by the bucket loop and the
-        sample-sharded path: the fused tree or MLP kernel when it applies,
-        else the synth + torch-module path."""
-        from . import mlp_pack
+        sample-sharded path: the fused tree, kernel-machine or MLP kernel
+        when it applies, else the synth + torch-module path."""
+        from . import km_pack, mlp_pack
 
         if self.trees_fused:
             return self._ey_fused_trees(masks, X_dev, varying)
+        if self.km_fused:
+            if len(varying) <= km_pack.MAX_GROUPS:
+                return self._ey_fused_km(masks, X_dev, varying)
+            self._km_log_fallback(
+                f"{len(varying)} varying groups (supported: <= "
+                f"{km_pack.MAX_GROUPS})"
+            )
         if self.mlp_fused:
             if len(varying) <= mlp_pack.MAX_GROUPS:
                 return self._ey_fused_mlp(masks, X_dev, varying)
@@ -436,6 +448,135 @@ class GpuKernelShap:
         return ey
 
     # ------------------------------------------------------------------ #
+    # KernelMachinePredictor: fused_predict_kernelmachine (K4k) with the
+    # GEMM-form torch module as the out-of-envelope fallback
+
+    def _init_kernel_machine(self, predictor):
+        from . import km_pack
+
+        t = self.torch
+        kc = self.engine.kernels
+        if kc.predict_dtype not in ("fp32", "fp64"):
+            raise ValueError(
+                f"predict_dtype={kc.predict_dtype!r} is not available for "
+                "KernelMachinePredictor (a bf16 distance under an "
+                "exponential is not a usable mode); supported: 'fp32' "
+                "(fused kernel-machine kernel) and 'fp64' (verification)"
+            )
+        if kc.module_autocast == "bf16":
+            raise ValueError(
+                "module_autocast='bf16' is not available for "
+                "KernelMachinePredictor: the distance expansion on the "
+                "torch-module path cancels, and bf16 leaves nothing of it"
+            )
+        params = predictor.kernel_machine_params()
+        # fp64 module on the device: per-instance totals and verification
+        self.km = {
+            "mod64": predictor.build_module(t.float64).to(self.device),
+            "act": params["activation"],
+            "n_sv": int(np.asarray(params["alpha"]).shape[1]),
+        }
+        # every module-path consumer (fallback, sample-sharded) keeps
+        # working; a fresh module, so the caller's predictor is not touched
+        self.module = predictor.build_module().to(self.device)
+        self._km_logged = False
+        if kc.predict_dtype == "fp64":
+            eng = self.engine
+            self.km["bg64"] = t.tensor(
+                eng.background, dtype=t.float64, device=self.device)
+            self.km["wbg64"] = t.tensor(
+                eng.bg_weights, dtype=t.float64, device=self.device)
+            self.km["fnull64"] = t.tensor(
+                eng.fnull, dtype=t.float64, device=self.device)
+            return
+        reason = (None if kc.fused_predict
+                  else "kernels.fused_predict is off")
+        reason = reason or km_pack.envelope_reason(params)
+        if reason is not None:
+            self._km_log_fallback(reason)
+            return
+        pack = km_pack.pack_machine(
+            params, self.engine._col_group, self.n_groups, self.device)
+        self.km["pack"] = pack
+        # fit-time constants shared by all instances
+        self.km["bgparts"] = km_pack.group_parts(pack, self.bg.double())  # (N,V,G)
+        self.km["base"] = km_pack.base(pack, self.km["bgparts"])          # (N,Vpad)
+        self.km["bg_img"] = {}
+        self.km_fused = True
+
+    def _km_log_fallback(self, reason):
+        if not self._km_logged:
+            logger.info(
+                "KernelMachinePredictor runs on the torch-module path, not "
+                "the fused kernel-machine kernel: %s", reason,
+            )
+            self._km_logged = True
+
+    def _ey_fused_km(self, masks, X_dev, varying):
+        """K4k: fused kernel-machine predict. Only ey (B,S,n_out) reaches
+        HBM; the workspaces are the operand images xp (B,Vpad,Mpad) and
+        bgpn (N,Vpad,Mpad), the latter cached per varying pattern. The
+        bucket is split along B so that one launch's workspaces stay within
+        ``km_pack.WORKSPACE_BYTES``."""
+        from . import km_pack
+
+        t = self.torch
+        b, s, m = masks.shape
+        km = self.km
+        pack = km["pack"]
+        vidx = t.tensor(varying, dtype=t.int64, device=self.device)
+        key = np.asarray(varying).tobytes()
+        bgpn = km["bg_img"].get(key)
+        if bgpn is None:
+            if len(km["bg_img"]) >= 8:
+                km["bg_img"].clear()
+            bgpn = km_pack.image(pack, km["bgparts"], vidx, negate=True)
+            km["bg_img"][key] = bgpn
+        masks = masks.contiguous()
+        ey = self._buf("ey", (b, s, self.n_out))
+        step = km_pack.instances_per_launch(pack, self.D, m)
+        X64 = X_dev.double()
+        for lo in range(0, b, step):
+            hi = min(lo + step, b)
+            xp = km_pack.image(
+                pack, km_pack.group_parts(pack, X64[lo:hi]), vidx)
+            km_pack.fused_predict(
+                self.ext, pack, masks[lo:hi], xp, bgpn, km["base"],
+                self.bg_w, ey[lo:hi])
+        return ey
+
+    def _ey_km_f64(self, masks, X_dev, varying, budget_bytes=256 << 20):
+        """fp64 verification path for KernelMachinePredictor
+        (predict_dtype='fp64'): explicit masked blend + the fp64 module on
+        the SAME device masks, chunked like ``_ey_mlp_f64``."""
+        t = self.torch
+        b, s, m = masks.shape
+        vmap = np.full(self.n_groups, m, dtype=np.int64)
+        for i, g in enumerate(varying):
+            vmap[g] = i
+        colk = t.tensor(vmap[self.engine._col_group], device=self.device)
+        bg = self.km["bg64"]
+        X64 = X_dev.double()
+        wbg64 = self.km["wbg64"]
+        width = max(self.D, self.km["n_sv"])
+        s_chunk = max(1, budget_bytes // (8 * 3 * b * self.N * width))
+        ey = t.empty(b, s, self.n_out, dtype=t.float64, device=self.device)
+        zero_col = t.zeros(b, 1, 1, dtype=t.bool, device=self.device)
+        for lo in range(0, s, s_chunk):
+            hi = min(lo + s_chunk, s)
+            mk = masks[:, lo:hi].bool()
+            # non-varying columns map to an always-off sentinel column m
+            mk = t.cat([mk, zero_col.expand(b, hi - lo, 1)], dim=2)[:, :, colk]
+            rows = t.where(
+                mk[:, :, None, :], X64[:, None, None, :], bg[None, None, :, :]
+            )                                             # (b, sc, N, D)
+            with t.no_grad():
+                p = self.km["mod64"](rows.reshape(-1, self.D))
+            p = p.view(b, hi - lo, self.N, self.n_out)
+            ey[:, lo:hi] = t.einsum("bsno,n->bso", p, wbg64)
+        return ey
+
+    # ------------------------------------------------------------------ #
 
     def _link(self, p):
         t = self.torch
@@ -463,6 +604,9 @@ class GpuKernelShap:
         if self.trees is not None:
             with t.no_grad():
                 return self.trees["mod64"](rows)
+        if self.km is not None:
+            with t.no_grad():
+                return self.km["mod64"](rows)
         with t.no_grad():
             return self.module(rows).double()
 
@@ -948,6 +1092,8 @@ class GpuKernelShap:
         if self.trees_fused:
             # packed decisions dx plus the (T, 64) comparison image behind them
             per_inst += self.trees["pack"]["n_trees"] * (8 + 64 * 9)
+        # (the fused kernel-machine workspaces are bounded per launch,
+        # km_pack.WORKSPACE_BYTES, not per instance)
         return max(1, self._CHUNK_BYTES // per_inst)
 
     def shap_values(
@@ -1009,9 +1155,10 @@ class GpuKernelShap:
 
         fp64 = self.engine.kernels.predict_dtype == "fp64"
         X64_dev = None
-        f64c = self.mlp if self.mlp is not None else self.trees
+        f64c = next((c for c in (self.mlp, self.trees, self.km)
+                     if c is not None), None)
         if fp64 and f64c is not None:
-            # MLP / tree verification mode: inputs stay fp64 end to end (the
+            # MLP / tree / kernel-machine verification mode: inputs stay fp64 end to end (the
             # fp32 rounding of x alone shifts phi by ~1e-7)
             X64_dev = (X.to(self.device).double() if t.is_tensor(X)
                        else t.tensor(X, dtype=t.float64, device=self.device))
@@ -1331,7 +1478,8 @@ class GpuKernelShap:
         device masks, exact fp64 kernel weights (rebuilt from the plan's
         fp64 arrays, not the fp32 device copy), fp64 link and WLS."""
         t = self.torch
-        if self.linear is None and self.mlp is None and self.trees is None:
+        if self.linear is None and self.mlp is None and self.trees is None \
+                and self.km is None:
             raise TypeError(
                 "predict_dtype='fp64' is the linear-predictor verification "
                 "mode; torch-module predictors have no fp64 reference "
@@ -1342,6 +1490,8 @@ class GpuKernelShap:
             ey = self._ey_mlp_f64(masks, sub_X, varying)
         elif self.trees is not None:
             ey = self._ey_trees_f64(masks, sub_X, varying)
+        elif self.km is not None:
+            ey = self._ey_km_f64(masks, sub_X, varying)
         else:
             ey = self._ey_linear_f64(masks, sub_X, varying)
         kw64 = t.from_numpy(

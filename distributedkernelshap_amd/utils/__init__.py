@@ -160,8 +160,9 @@ def load_model(path: str = None):
     """Unpickle a predictor; sklearn LogisticRegression is wrapped into the
     native LinearPredictor and sklearn MLPClassifier / MLPRegressor into
     the native MLPPredictor, and sklearn decision trees, forests and
-    gradient boosting into the native TreeEnsemblePredictor, so the fused
-    GPU paths apply (reference ``load_model``, utils.py:137-157)."""
+    gradient boosting into the native TreeEnsemblePredictor, and sklearn
+    kernel SVMs / kernel ridge into the native KernelMachinePredictor, so
+    the fused GPU paths apply (reference ``load_model``, utils.py:137-157)."""
     import pickle
 
     path = path or os.path.join(ASSETS_DIR, "predictor.pkl")
@@ -189,6 +190,12 @@ def load_model(path: str = None):
         from ..models.predictors import TreeEnsemblePredictor
 
         return TreeEnsemblePredictor.from_sklearn(obj)
+    if type(obj).__module__.startswith(("sklearn.svm", "sklearn.kernel_ridge")):
+        # kernel SVM / kernel ridge (a linear-kernel SVC went through coef_
+        # above); raises TypeError with the reason for an unsupported one
+        from ..models.predictors import KernelMachinePredictor
+
+        return KernelMachinePredictor.from_sklearn(obj)
     if not callable(obj):
         raise TypeError(f"loaded object {type(obj)} is not a predictor")
     return obj
