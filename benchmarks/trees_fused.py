@@ -4,7 +4,9 @@ Default shape: 256 instances, 100 background rows, 64 features (64 singleton
 groups), 100 trees of depth 4, default sample count, ``l1_reg=False``. Paths:
 
   module   make_predictor("trees")        gather-traversal module on synth rows
-  fused    make_predictor("trees_fused")  fused_predict_trees
+  fused    make_predictor("trees_fused")  fused_predict_trees, or
+                                          fused_predict_trees_walk for trees
+                                          of more than 64 internal nodes
   cpu      make_predictor("trees_fused")  CPU engine on ``--cpu-instances`` rows
 
 Each path runs in a child process of its own under a time limit; the driver
@@ -17,6 +19,9 @@ paths print a per-stage trace.
 
     python benchmarks/trees_fused.py                 # all three paths
     python benchmarks/trees_fused.py --path fused
+    # a forest shape (about 280 internal nodes per tree): the walk kernel;
+    # the module path explains fewer rows so that it ends within --timeout
+    python benchmarks/trees_fused.py --depth 12 --p-stop 0.2 --module-instances 8
 """
 from __future__ import annotations
 
@@ -52,11 +57,14 @@ def run_path(args) -> dict:
         raise SystemExit("trees_fused.py measures on a GPU; none is visible")
     kind, device = PATHS[args.path]
     instances = args.cpu_instances if device == "cpu" else args.instances
+    if args.path == "module" and args.module_instances is not None:
+        instances = args.module_instances
     data = make_tabular(
         n_features=64, n_instances=args.instances,
         n_background=args.background, seed=1000,
     )
-    pred = make_predictor(kind, 64, 2, seed=0, trees=args.trees, depth=args.depth)
+    pred = make_predictor(kind, 64, 2, seed=0, trees=args.trees,
+                          depth=args.depth, p_stop=args.p_stop)
     engine = KernelShapEngine(
         pred, data.background, groups=data.groups, link="logit", seed=0,
         device=device,
@@ -95,6 +103,7 @@ def run_path(args) -> dict:
     if device == "cpu":
         return res
     res["trees_fused"] = bool(getattr(engine._gpu, "trees_fused", False))
+    res["trees_kernel"] = getattr(engine._gpu, "trees_kernel", None)
     if kind == "trees_fused":
         assert res["trees_fused"], "fused path expected but not taken"
         k = min(args.selfcheck, instances)
@@ -126,6 +135,11 @@ def main() -> None:
     ap.add_argument("--background", type=int, default=100)
     ap.add_argument("--trees", type=int, default=100)
     ap.add_argument("--depth", type=int, default=4)
+    ap.add_argument("--p-stop", type=float, default=0.2,
+                    help="probability that a branch below the root ends early")
+    ap.add_argument("--module-instances", type=int, default=None,
+                    help="instances the module path explains (default: "
+                         "--instances); for deep shapes")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--selfcheck", type=int, default=8,
@@ -145,10 +159,13 @@ def main() -> None:
     passthrough = [
         "--instances", str(args.instances), "--background", str(args.background),
         "--trees", str(args.trees), "--depth", str(args.depth),
+        "--p-stop", str(args.p_stop),
         "--steps", str(args.steps), "--warmup", str(args.warmup),
         "--selfcheck", str(args.selfcheck),
         "--cpu-instances", str(args.cpu_instances),
     ]
+    if args.module_instances is not None:
+        passthrough += ["--module-instances", str(args.module_instances)]
     for name in ("module", "fused", "cpu"):
         cmd = [sys.executable, os.path.abspath(__file__), "--path", name]
         try:

@@ -286,9 +286,10 @@ class TreeEnsemblePredictor:
     The comparison rule is sklearn's: the input is rounded to float32 and
     ``float64(x32) <= threshold`` goes left. ``__call__`` is the numpy oracle
     with exactly this rule; ``tree_params()`` is the protocol hook the GPU
-    engine uses to run the fused ``fused_predict_trees`` HIP kernel;
-    ``torch_module()`` is the fp32 gather-traversal ``nn.Module`` used when
-    the ensemble is outside that kernel's envelope.
+    engine uses to run the fused HIP kernels (``fused_predict_trees`` for
+    trees of at most 64 internal nodes, ``fused_predict_trees_walk`` for
+    deeper ones); ``torch_module()`` is the fp32 gather-traversal
+    ``nn.Module`` used when the ensemble is outside both envelopes.
 
     NaN inputs are not supported: sklearn >= 1.3 routes a missing value per
     node (``missing_go_to_left``), which these tables do not carry.
@@ -895,6 +896,7 @@ def make_predictor(kind: str, d: int, n_out: int = 2, seed: int = 0, **kw):
             d, n_out, trees=kw.get("trees", 100), depth=kw.get("depth", 4),
             seed=seed, activation=kw.get("activation", "softmax"),
             vector_leaves=kw.get("vector_leaves", False),
+            p_stop=kw.get("p_stop", 0.2),
         )
         if kind == "trees_fused":
             return pred

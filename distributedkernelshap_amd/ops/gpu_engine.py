@@ -7,6 +7,7 @@ Per instance-bucket (instances sharing a varying-group pattern):
   fused_predict_linear (HIP K3-K6, MFMA)  -> ey (B,S,n_out)   [linear predictor]
      — or — fused_predict_mlp (HIP K4m, MFMA)  -> ey        [MLP predictor]
      — or — fused_predict_trees (HIP K4t)      -> ey        [tree ensemble]
+     — or — fused_predict_trees_walk (HIP K4w) -> ey        [deep trees]
      — or — fused_predict_kernelmachine (K4k)  -> ey        [SVM / kernel ridge]
      — or — synth_chunk (HIP K3') + torch module + weighted mean  [torch predictor]
   link transform (torch, fp32)           -> eyAdj
@@ -87,7 +88,8 @@ class GpuKernelShap:
         self.mlp = None          # fp64 weights + operand images (MLPPredictor)
         self.mlp_fused = False   # True when fused_predict_mlp serves this engine
         self.trees = None        # fp64 module + packed tables (TreeEnsemblePredictor)
-        self.trees_fused = False  # True when fused_predict_trees serves this engine
+        self.trees_fused = False  # True when a fused tree kernel serves this engine
+        self.trees_kernel = None  # "bits" (K4t), "walk" (K4w) or None (module)
         self.km = None           # fp64 module + operand images (KernelMachinePredictor)
         self.km_fused = False    # True when fused_predict_kernelmachine serves this engine
         lp = getattr(engine.predictor, "linear_params", None)
@@ -381,7 +383,15 @@ class GpuKernelShap:
             return
         reason = (None if kc.fused_predict
                   else "kernels.fused_predict is off")
-        reason = reason or tree_pack.envelope_reason(params)
+        walk = False
+        if reason is None:
+            reason = tree_pack.envelope_reason(params)
+            if reason is not None:
+                # beyond one u64 of split decisions per tree: the walk kernel
+                walk_reason = tree_pack.walk_envelope_reason(
+                    params, self.D, self.n_groups)
+                walk = walk_reason is None
+                reason = None if walk else f"{reason}; {walk_reason}"
         if reason is not None:
             # fit time only, so the reason is logged once per engine
             logger.info(
@@ -389,17 +399,24 @@ class GpuKernelShap:
                 "not the fused tree kernel: %s", reason,
             )
             return
+        if walk:
+            self.trees["pack"] = tree_pack.pack_trees_walk(
+                params, self.engine._col_group, self.device)
+            self.trees_fused = True
+            self.trees_kernel = "walk"
+            return
         pack = tree_pack.pack_trees(params, self.engine._col_group, self.device)
         self.trees["pack"] = pack
         # fit-time constant shared by all instances: the background rows'
         # split decisions, one u64 per (row, tree)
         self.trees["dbg"] = tree_pack.decision_bits(pack, self.bg)
         self.trees_fused = True
+        self.trees_kernel = "bits"
 
     def _ey_fused_trees(self, masks, X_dev, varying):
-        """K4t: fused tree predict. Only ey (B,S,n_out) reaches HBM; the
-        per-call operands are the instances' packed decisions dx (B,T) and
-        the group -> varying-index table."""
+        """K4t / K4w: fused tree predict. Only ey (B,S,n_out) reaches HBM;
+        the per-call operands are the group -> varying-index table and, for
+        the bit-register kernel, the instances' packed decisions dx (B,T)."""
         from . import tree_pack
 
         t = self.torch
@@ -408,8 +425,14 @@ class GpuKernelShap:
         vmap_h = np.full(self.n_groups, -1, dtype=np.int32)
         vmap_h[np.asarray(varying)] = np.arange(m, dtype=np.int32)
         vmap = t.tensor(vmap_h, device=self.device)
-        dx = tree_pack.decision_bits(pack, X_dev)
         ey = self._buf("ey", (b, s, self.n_out))
+        if self.trees_kernel == "walk":
+            # K4w reads the float32 rows themselves: no decision bits
+            return tree_pack.fused_predict_walk(
+                self.ext, pack, masks.contiguous(), vmap,
+                X_dev.float().contiguous(), self.bg, self.bg_w, ey,
+            )
+        dx = tree_pack.decision_bits(pack, X_dev)
         return tree_pack.fused_predict(
             self.ext, pack, masks.contiguous(), vmap, dx, self.trees["dbg"],
             self.bg_w, ey,
@@ -1089,8 +1112,9 @@ class GpuKernelShap:
             # and H1pad x G result) + the xp1 operand image (H1pad x Mpad)
             h1 = self.mlp["pack"]["hpad"][0]
             per_inst += 8 * g * (self.D + 2 * h1) + 4 * h1 * (g + 31)
-        if self.trees_fused:
+        if self.trees_kernel == "bits":
             # packed decisions dx plus the (T, 64) comparison image behind them
+            # (the walk kernel reads x itself and has no per-instance workspace)
             per_inst += self.trees["pack"]["n_trees"] * (8 + 64 * 9)
         # (the fused kernel-machine workspaces are bounded per launch,
         # km_pack.WORKSPACE_BYTES, not per instance)

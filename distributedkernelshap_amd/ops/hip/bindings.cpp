@@ -86,6 +86,14 @@ extern "C" int launch_fused_predict_trees(
     int B, int S, int Mv, int N, int T, int G, int E, int L, int C,
     int max_internal, int n_out, int act, int leaf_mode, hipStream_t stream);
 
+// tree_walk_kernels.hip
+extern "C" int launch_fused_predict_trees_walk(
+    const uint8_t* masks, const int* vmap, const float* x, const float* bg,
+    const int* nodes, const int* roots, const float* leaves, const float* base,
+    const float* wbg, float* ey, float scale,
+    int B, int S, int Mv, int N, int D, int G, int T, int R, int L,
+    int max_depth, int n_out, int act, int leaf_mode, hipStream_t stream);
+
 // km_kernels.hip
 extern "C" int launch_fused_predict_kernelmachine(
     const uint8_t* masks, const float* xp, const float* bgpn,
@@ -478,6 +486,62 @@ void fused_predict_trees(
     TORCH_CHECK(rc == 0, envelope);
 }
 
+void fused_predict_trees_walk(
+    torch::Tensor masks, torch::Tensor vmap, torch::Tensor x, torch::Tensor bg,
+    torch::Tensor nodes, torch::Tensor roots, torch::Tensor leaves,
+    torch::Tensor base, double scale, torch::Tensor wbg, torch::Tensor ey,
+    int64_t act, int64_t leaf_mode, int64_t max_depth) {
+    static const char* envelope =
+        "fused_predict_trees_walk: outside the supported envelope (depth <= "
+        "64, n_out <= 8, at most 1024 groups and 4096 features, node records "
+        "indexed by int32)";
+    CHECK_DEV(masks); CHECK_DEV(vmap); CHECK_DEV(x); CHECK_DEV(bg);
+    CHECK_DEV(nodes); CHECK_DEV(roots); CHECK_DEV(leaves); CHECK_DEV(base);
+    CHECK_DEV(wbg); CHECK_DEV(ey);
+    TORCH_CHECK(masks.dtype() == torch::kUInt8 && masks.dim() == 3,
+                "masks must be u8 (B,S,Mv)");
+    TORCH_CHECK(ey.dtype() == torch::kFloat32 && ey.dim() == 3,
+                "ey must be f32 (B,S,n_out)");
+    const int B = masks.size(0), S = masks.size(1), Mv = masks.size(2);
+    const int n_out = ey.size(2);
+    TORCH_CHECK(ey.size(0) == B && ey.size(1) == S, "ey must be f32 (B,S,n_out)");
+    TORCH_CHECK(vmap.dtype() == torch::kInt32 && vmap.dim() == 1,
+                "the group table must be int32 (G)");
+    TORCH_CHECK(x.dtype() == torch::kFloat32 && x.dim() == 2 && x.size(0) == B,
+                "x must be f32 (B,D)");
+    const int64_t D = x.size(1);
+    TORCH_CHECK(bg.dtype() == torch::kFloat32 && bg.dim() == 2
+                && bg.size(1) == D, "bg must be f32 (N,D)");
+    const int N = bg.size(0);
+    TORCH_CHECK(nodes.dtype() == torch::kInt32 && nodes.dim() == 2
+                && nodes.size(1) == 4, "nodes must be int32 (R,4)");
+    TORCH_CHECK(roots.dtype() == torch::kInt32 && roots.dim() == 1,
+                "roots must be int32 (T)");
+    TORCH_CHECK(leaf_mode == 0 || leaf_mode == 1, "leaf_mode must be 0 or 1");
+    TORCH_CHECK(leaves.dtype() == torch::kFloat32
+                && (leaf_mode == 0 ? leaves.dim() == 1
+                                   : (leaves.dim() == 2 && leaves.size(1) == n_out)),
+                "leaves must be f32 (L) for scalar or (L,n_out) for vector leaves");
+    TORCH_CHECK(base.dtype() == torch::kFloat32 && base.numel() == n_out,
+                "base must be f32 (n_out)");
+    TORCH_CHECK(wbg.dtype() == torch::kFloat32 && wbg.numel() == N,
+                "wbg must be f32 (N)");
+    TORCH_CHECK(max_depth >= 0 && max_depth <= 64, envelope);
+    TORCH_CHECK(nodes.size(0) <= 0x7fffffffLL && leaves.size(0) <= 0x7fffffffLL
+                && roots.size(0) <= 0x7fffffffLL && D <= 0x7fffffffLL
+                && vmap.size(0) <= 0x7fffffffLL, envelope);
+    int rc = launch_fused_predict_trees_walk(
+        masks.data_ptr<uint8_t>(), vmap.data_ptr<int>(), x.data_ptr<float>(),
+        bg.data_ptr<float>(), nodes.data_ptr<int>(), roots.data_ptr<int>(),
+        leaves.data_ptr<float>(), base.data_ptr<float>(), wbg.data_ptr<float>(),
+        ey.data_ptr<float>(), (float)scale, B, S, Mv, N, (int)D,
+        (int)vmap.size(0), (int)roots.size(0), (int)nodes.size(0),
+        (int)leaves.size(0), (int)max_depth, n_out, (int)act, (int)leaf_mode,
+        current_stream());
+    TORCH_CHECK(rc != -2, "fused_predict_trees_walk: LDS size attribute rejected");
+    TORCH_CHECK(rc == 0, envelope);
+}
+
 void fused_predict_kernelmachine(
     torch::Tensor masks, torch::Tensor xp, torch::Tensor bgpn,
     torch::Tensor base, torch::Tensor alpha, torch::Tensor intercept,
@@ -545,6 +609,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("base"), pybind11::arg("scale"), pybind11::arg("wbg"),
           pybind11::arg("ey"), pybind11::arg("act"), pybind11::arg("leaf_mode"),
           pybind11::arg("max_internal"));
+    m.def("fused_predict_trees_walk", &fused_predict_trees_walk,
+          "fused deep-tree predict (K4w): 16-byte node records walked on the "
+          "blended row, group bitset per sample, x row and background in LDS",
+          pybind11::arg("masks"), pybind11::arg("vmap"), pybind11::arg("x"),
+          pybind11::arg("bg"), pybind11::arg("nodes"), pybind11::arg("roots"),
+          pybind11::arg("leaves"), pybind11::arg("base"),
+          pybind11::arg("scale"), pybind11::arg("wbg"), pybind11::arg("ey"),
+          pybind11::arg("act"), pybind11::arg("leaf_mode"),
+          pybind11::arg("max_depth"));
     m.def("fused_predict_mlp", &fused_predict_mlp,
           "fused MLP predict (K4m): first layer folded over varying groups, "
           "hidden activations in LDS, f32 or bf16 MFMA by operand dtype",

@@ -1,4 +1,5 @@
-"""Packed tables for the fused tree predict kernel (``fused_predict_trees``).
+"""Packed tables for the fused tree predict kernels (``fused_predict_trees``
+and, for deep trees, ``fused_predict_trees_walk``).
 
 Everything here is numpy on the host plus plain torch on small tensors: the
 tables are built once per engine, ``decision_bits`` runs once at fit for the
@@ -24,6 +25,35 @@ Per-tree layout (matching ``ops/hip/tree_kernels.hip``):
 
 A tree that is a single leaf gets one dummy internal node whose children are
 both that leaf.
+
+Deep trees (``fused_predict_trees_walk``, ``ops/hip/tree_walk_kernels.hip``)
+use a second, independent set of tables built by ``pack_trees_walk``:
+
+  nodes       (R, 4) int32            one 16-byte record per node, internal
+                                      nodes and leaves alike.  The nodes of a
+                                      tree are numbered in preorder and the
+                                      trees follow each other, so record
+                                      ``roots[t]`` is tree t's root and the
+                                      left child of record i is record i + 1.
+                                      split: [0] the bits of the float32
+                                               ``floor_f32(threshold)``
+                                             [1] feature (>= 0)
+                                             [2] coalition group of the feature
+                                             [3] record index of the right child
+                                      leaf:  [0] the bits of the float32 leaf
+                                                 value (scalar leaves; the
+                                                 kernel reads it here), 0 for
+                                                 vector leaves
+                                             [1] -1
+                                             [2] output column (0 for vector
+                                                 leaves)
+                                             [3] row of ``leaves``
+                                      A float32 row value v goes left when
+                                      ``v <= thr32``.
+  roots       (T,) int32              record index of each tree's root
+  leaves      (L,) or (L, n_out) f32  leaf values, trees in order, a tree's
+                                      leaves in preorder (the kernel reads
+                                      the vector form only)
 """
 from __future__ import annotations
 
@@ -34,6 +64,12 @@ MAX_NOUT = 8
 MAX_TREES = 1024
 LDS_BYTES = 160 * 1024
 _THREADS = 1024       # workgroup size of the kernel (reduction scratch)
+
+# envelope of the walk kernel for deep trees
+WALK_MAX_DEPTH = 64       # step bound of one walk
+WALK_MAX_GROUPS = 1024    # group bitset: 16 u64 words per sample in LDS
+WALK_MAX_FEATURES = 4096  # x row: 16 KiB of LDS
+WALK_MAX_RECORDS = 2**31 - 1
 
 ACT_CODE = {"none": 0, "sigmoid": 1, "softmax": 2}
 
@@ -179,6 +215,109 @@ def decision_bits(pack: dict, rows):
         # disjoint bits: the wrapping int64 sum is the OR, bit 63 included
         out[lo : lo + step] = (go_left.to(t.int64) << shifts).sum(dim=-1)
     return out
+
+
+def _preorder(left, right):
+    """Nodes of one tree in preorder (left subtree first) and its depth in
+    splits along the longest path."""
+    order, depth = [], 0
+    stack = [(0, 0)]
+    while stack:
+        i, d = stack.pop()
+        order.append(i)
+        if left[i] >= 0:
+            stack.append((int(right[i]), d + 1))
+            stack.append((int(left[i]), d + 1))
+        elif d > depth:
+            depth = d
+    return order, depth
+
+
+def walk_envelope_reason(params: dict, n_features: int, n_groups: int):
+    """None when the ensemble fits the walk kernel for deep trees, else a
+    one-line reason."""
+    depth = max(_preorder(np.asarray(tr["left"]), np.asarray(tr["right"]))[1]
+                for tr in params["trees"])
+    if depth > WALK_MAX_DEPTH:
+        return f"depth {depth} (walk kernel: <= {WALK_MAX_DEPTH})"
+    if params["n_out"] > MAX_NOUT:
+        return f"n_out {params['n_out']} (walk kernel: <= {MAX_NOUT})"
+    if n_groups > WALK_MAX_GROUPS:
+        return f"{n_groups} groups (walk kernel: <= {WALK_MAX_GROUPS})"
+    if n_features > WALK_MAX_FEATURES:
+        return f"{n_features} features (walk kernel: <= {WALK_MAX_FEATURES})"
+    records = sum(len(tr["left"]) for tr in params["trees"])
+    if records > WALK_MAX_RECORDS:
+        return f"{records} nodes (walk kernel: <= {WALK_MAX_RECORDS})"
+    return None
+
+
+def pack_trees_walk(params: dict, col_group, device) -> dict:
+    """Device tables of the walk kernel (layout in the module docstring) for
+    ``tree_params()`` output ``params`` and the feature -> group map
+    ``col_group`` (D,). No envelope check: the kernel binding is the one
+    place that refuses unsupported ensembles."""
+    import torch as t
+
+    from ..models.tree_module import floor_f32
+
+    trees = params["trees"]
+    col_group = np.asarray(col_group, dtype=np.int64)
+    vector = params["out_col"] is None
+    nodes, roots, leaves = [], [], []
+    off = n_leaf = max_depth = 0
+    for ti, tr in enumerate(trees):
+        left = np.asarray(tr["left"], dtype=np.int64)
+        right = np.asarray(tr["right"], dtype=np.int64)
+        feature = np.asarray(tr["feature"], dtype=np.int64)
+        order, depth = _preorder(left, right)
+        order = np.asarray(order, dtype=np.int64)
+        max_depth = max(max_depth, depth)
+        pos = np.empty(left.shape[0], dtype=np.int64)
+        pos[order] = np.arange(order.shape[0]) + off
+        internal = left[order] >= 0
+        feat = np.where(internal, feature[order], 0)
+        leaf_row = n_leaf + np.cumsum(~internal) - 1
+        rec = np.empty((order.shape[0], 4), dtype=np.int32)
+        thr32 = floor_f32(np.asarray(tr["threshold"], dtype=np.float64)[order])
+        value = np.asarray(tr["value"], dtype=np.float64)[order]
+        leaf_bits = (np.zeros(order.shape[0], dtype=np.int32) if vector
+                     else value.astype(np.float32).view(np.int32))
+        rec[:, 0] = np.where(internal, thr32.view(np.int32), leaf_bits)
+        rec[:, 1] = np.where(internal, feat, -1)
+        rec[:, 2] = np.where(internal, col_group[feat],
+                             0 if vector else int(params["out_col"][ti]))
+        rec[:, 3] = np.where(internal, pos[np.maximum(right[order], 0)], leaf_row)
+        nodes.append(rec)
+        roots.append(off)
+        leaves.append(value[~internal])
+        off += order.shape[0]
+        n_leaf += int((~internal).sum())
+
+    def dev(a):
+        return t.from_numpy(np.ascontiguousarray(a)).to(device)
+
+    return {
+        "n_trees": len(trees), "n_out": int(params["n_out"]),
+        "leaf_mode": 1 if vector else 0, "max_depth": int(max_depth),
+        "nodes": dev(np.concatenate(nodes)),
+        "roots": dev(np.asarray(roots, dtype=np.int32)),
+        "leaves": dev(np.concatenate(leaves).astype(np.float32)),
+        "base": dev(np.asarray(params["base"], dtype=np.float32)),
+        "scale": float(params["scale"]),
+        "act": ACT_CODE[params["activation"]],
+    }
+
+
+def fused_predict_walk(ext, pack: dict, masks, vmap, x, bg, wbg, ey):
+    """Launch ``fused_predict_trees_walk`` with the packed tables; ``x``
+    (B, D) and ``bg`` (N, D) are the float32 rows themselves."""
+    ext.fused_predict_trees_walk(
+        masks, vmap, x, bg, pack["nodes"], pack["roots"], pack["leaves"],
+        pack["base"], pack["scale"], wbg, ey, pack["act"], pack["leaf_mode"],
+        pack["max_depth"],
+    )
+    return ey
 
 
 def fused_predict(ext, pack: dict, masks, vmap, dx, dbg, wbg, ey):

@@ -22,6 +22,7 @@ try:
                 "distributedkernelshap_amd/ops/hip/kshap_kernels.hip",
                 "distributedkernelshap_amd/ops/hip/mlp_kernels.hip",
                 "distributedkernelshap_amd/ops/hip/tree_kernels.hip",
+                "distributedkernelshap_amd/ops/hip/tree_walk_kernels.hip",
                 "distributedkernelshap_amd/ops/hip/km_kernels.hip",
             ],
             extra_compile_args={
