@@ -13,6 +13,15 @@ Per instance-bucket (instances sharing a varying-group pattern):
   link transform (torch, fp32)           -> eyAdj
   wls_solve (HIP K7)                     -> phi (B,M,n_out)
 
+The fp32 linear predictor with at most 64 varying groups, (M-1)+n_out <= 16
+and l1 selection off (the headline configuration) runs the packed pipeline
+instead, four kernels from the instances to phi_full, with no u8 masks:
+
+  fill_masks_packed (K2p)            -> packed (B,S) u64 mask words
+  linear_prepare (K0p)               -> diff image, total (B,n_out)
+  fused_predict_linear_packed (K3p)  -> eyAdj (link fused)
+  wls_solve_packed (K7p)             -> phi_full (B,n_groups,n_out)
+
 The reference's equivalent work is the per-instance shap 0.35.0 loop invoked
 from ``explainers/kernel_shap.py:250``: sampling -> synth -> predict_proba ->
 mean -> WLS, one instance at a time on one CPU core. Here the whole
@@ -147,7 +156,8 @@ class GpuKernelShap:
         # hipMalloc stalls measured at B=2560)
         self._ws: dict = {}
         self.trace: dict = None  # per-stage ms lists when tracing enabled
-        # hipGraph capture of the fused pipeline (~60 fixed-shape launches):
+        # hipGraph capture of the fused pipeline (4 fixed-shape launches on
+        # the packed path, ~45 on the u8-mask path):
         # keyed by (B, nsamples, varying pattern, offset); disable with
         # KSHAP_GRAPH=0 or automatically on capture failure
         self._graphs: dict = {}
@@ -993,6 +1003,112 @@ class GpuKernelShap:
         return ey
 
     # ------------------------------------------------------------------ #
+    # packed linear pipeline: four kernels from X to phi_full
+
+    def _packed_ok(self, m, plan, l1_reg) -> bool:
+        """Whether a bucket of ``m`` varying groups runs the packed pipeline
+        (K2p, K0p, K3p, K7p). Everything else keeps the u8-mask path."""
+        kc = self.engine.kernels
+        return (
+            self.linear is not None
+            and kc.predict_dtype == "fp32"
+            and kc.fused_predict
+            and kc.wls_mode in ("auto", "mfma")
+            and 2 <= m <= 64
+            and (self.N + 15) // 16 * 16 <= 128
+            and self.n_out in (1, 2, 4)
+            and (m - 1) + self.n_out <= 16
+            and not self._l1_active(plan, l1_reg)
+        )
+
+    def _packed_consts(self):
+        """Operands that depend only on the fitted engine: padded base / wbg
+        images and the link of fnull (fp64 for the totals, fp32 for ey)."""
+        c = getattr(self, "_packed_c", None)
+        if c is None:
+            t = self.torch
+            act, oimg = self._act_oimg()
+            npad = (self.N + 15) // 16 * 16
+            base = t.zeros(oimg, npad, device=self.device)
+            base[:, : self.N] = self._base_img(act)
+            wbg = t.zeros(npad, device=self.device)
+            wbg[: self.N] = self.bg_w
+            lfnull64 = self._link(self.fnull.double()).contiguous()
+            c = {
+                "act": act, "oimg": oimg, "npad": npad, "base": base,
+                "wbg": wbg, "lfnull64": lfnull64,
+                "lfnull": lfnull64.float().contiguous(),
+                "bgp": self._bg_part_img(act).contiguous(),
+                "link": 0 if self.link_name == "identity" else 1,
+            }
+            self._packed_c = c
+        return c
+
+    def _packed_plan(self, plan):
+        """Per-plan operands: enumerated rows as packed words, the (S,)
+        kernel-weight vector, and the sampler's size table."""
+        t = self.torch
+        key = ("packed", plan.m, plan.nsamples)
+        ent = self._enum_cache.get(key)
+        if ent is None:
+            ne = plan.enum_masks.shape[0]
+            enum_packed = t.empty(1, ne, dtype=t.int64, device=self.device)
+            if ne > 0:
+                enum = t.tensor(plan.enum_masks, dtype=t.uint8,
+                                device=self.device)
+                self.ext.pack_masks(enum[None].contiguous(), enum_packed)
+            kw = t.empty(plan.nsamples, dtype=t.float32, device=self.device)
+            kw[:ne] = t.tensor(plan.enum_weights, dtype=t.float32,
+                               device=self.device)
+            if plan.n_random > 0:
+                kw[ne:] = plan.weight_left / plan.n_random
+            cdf = t.tensor(
+                np.cumsum(plan.random_size_probs).astype(np.float32),
+                device=self.device,
+            )
+            szs = t.tensor(plan.random_sizes.astype(np.int32),
+                           device=self.device)
+            ent = (enum_packed[0].contiguous(), kw, cdf, szs)
+            self._enum_cache[key] = ent
+        return ent
+
+    def _packed_pipeline(self, X_dev, plan, vidx_t, ids_dev, phi_full,
+                         timer=None):
+        """X_dev (b, D) -> phi_full (b, n_groups, n_out), every element
+        written. Shared by the captured graph body and the eager bucket loop,
+        so replayed and eager results come from the same kernels. ``timer``
+        (eager only) records the usual stage names."""
+        t = self.torch
+        b = X_dev.shape[0]
+        m, s = plan.m, plan.nsamples
+        c = self._packed_consts()
+        enum_packed, kw, cdf, szs = self._packed_plan(plan)
+        mpad = max(4, (m + 3) // 4 * 4)
+        packed = self._buf("packed", (b, s), t.int64)
+        self.ext.fill_masks_packed(
+            packed, enum_packed, plan.n_random, cdf, szs,
+            int(np.floor((m - 1) / 2.0)), int(self.engine.seed), ids_dev, m,
+        )
+        if timer is not None:
+            timer.mark("masks")
+        diff = self._buf(f"diffp{m}", (b, c["oimg"], mpad, c["npad"]))
+        total = self._buf("totalp", (b, self.n_out))
+        self.ext.linear_prepare(
+            X_dev, self.linear["W"], self.linear["b"], self.col_group, vidx_t,
+            c["bgp"], c["lfnull64"], diff, total, c["act"], c["link"],
+        )
+        ey = self._buf("ey", (b, s, self.n_out))
+        self.ext.fused_predict_linear_packed(
+            packed, diff, c["base"], c["wbg"], ey, c["act"], c["link"],
+            c["lfnull"],
+        )
+        if timer is not None:
+            timer.mark("predict")
+        self.ext.wls_solve_packed(packed, kw, ey, total, vidx_t, phi_full)
+        if timer is not None:
+            timer.mark("wls")
+
+    # ------------------------------------------------------------------ #
     # hipGraph fast path
 
     def _fused_body(self, X_dev, plan, varying, vidx_t, ids_dev, phi_full):
@@ -1002,6 +1118,10 @@ class GpuKernelShap:
         t = self.torch
         b = X_dev.shape[0]
         m = len(varying)
+        if self._packed_ok(m, plan, False):
+            # (the caller has already established that l1 is off)
+            self._packed_pipeline(X_dev, plan, vidx_t, ids_dev, phi_full)
+            return
         fx = self._predict_rows_f64(X_dev)
         lfx = self._link(fx)
         lfnull64 = self._link(self.fnull.double())
@@ -1092,11 +1212,21 @@ class GpuKernelShap:
     # whose projected footprint exceeds it are processed in instance chunks
     _CHUNK_BYTES = 2 << 30
 
-    def _instances_per_chunk(self, nsamples: Optional[int]) -> int:
+    def _instances_per_chunk(self, nsamples: Optional[int],
+                             l1_reg="auto") -> int:
         from ..core.sampler import default_nsamples
 
         s = nsamples or default_nsamples(max(2, self.n_groups))
         g = self.n_groups
+        if g >= 2 and self._packed_ok(g, self.engine._plan(g, nsamples),
+                                      l1_reg):
+            # packed pipeline (eligible at g groups, hence at any smaller
+            # varying count): packed u64 + ey f32 per sample, no u8 masks
+            # and no weight broadcast; diff image and totals per instance
+            npad = (self.N + 15) // 16 * 16
+            per_inst = (s * (8 + 4 * self.n_out)
+                        + 4 * self.n_out * (g + 3) * npad + (1 << 14))
+            return max(1, self._CHUNK_BYTES // per_inst)
         # masks u8 + packed u64 + kwb f32 + ey f32 (+ column-tile partials
         # on the tiled stress path) per instance
         npad = (self.N + 15) // 16 * 16
@@ -1134,7 +1264,7 @@ class GpuKernelShap:
         bounce."""
         t = self.torch
         b_total = X.shape[0]
-        chunk = self._instances_per_chunk(nsamples)
+        chunk = self._instances_per_chunk(nsamples, l1_reg)
         if b_total > chunk:
             # large batches stream through in fixed-size chunks (1M-instance
             # configs: the whole-batch mask tensor would be TB-scale)
@@ -1178,27 +1308,6 @@ class GpuKernelShap:
         timer.mark("h2d")
 
         fp64 = self.engine.kernels.predict_dtype == "fp64"
-        X64_dev = None
-        f64c = next((c for c in (self.mlp, self.trees, self.km)
-                     if c is not None), None)
-        if fp64 and f64c is not None:
-            # MLP / tree / kernel-machine verification mode: inputs stay fp64 end to end (the
-            # fp32 rounding of x alone shifts phi by ~1e-7)
-            X64_dev = (X.to(self.device).double() if t.is_tensor(X)
-                       else t.tensor(X, dtype=t.float64, device=self.device))
-        fx = self._predict_rows_f64(                    # (B, n_out) fp64
-            X_dev if X64_dev is None else X64_dev)
-        lfx = self._link(fx)
-        lfnull64 = self._link(
-            self.fnull.double() if X64_dev is None else f64c["fnull64"])
-        total_all = (lfx - lfnull64[None, :])           # (B, n_out) fp64
-        if not fp64:
-            total_all = total_all.float()
-        lfnull = lfnull64.float()
-
-        phi_full = t.zeros(b, self.n_groups, self.n_out, device=self.device,
-                           dtype=t.float64 if fp64 else t.float32)
-
         # speculative fast path: when the last call used a captured graph,
         # assume the varying pattern repeats, replay immediately and verify
         # the device-computed pattern probe in the SAME sync as the result
@@ -1246,6 +1355,29 @@ class GpuKernelShap:
                     ]
                 # pattern changed: discard the replayed result, run eagerly
                 self._spec = None
+
+        # per-instance totals and the result buffer: computed only once the
+        # speculative replay (which carries its own) is out of the picture
+        X64_dev = None
+        f64c = next((c for c in (self.mlp, self.trees, self.km)
+                     if c is not None), None)
+        if fp64 and f64c is not None:
+            # MLP / tree / kernel-machine verification mode: inputs stay fp64 end to end (the
+            # fp32 rounding of x alone shifts phi by ~1e-7)
+            X64_dev = (X.to(self.device).double() if t.is_tensor(X)
+                       else t.tensor(X, dtype=t.float64, device=self.device))
+        fx = self._predict_rows_f64(                    # (B, n_out) fp64
+            X_dev if X64_dev is None else X64_dev)
+        lfx = self._link(fx)
+        lfnull64 = self._link(
+            self.fnull.double() if X64_dev is None else f64c["fnull64"])
+        total_all = (lfx - lfnull64[None, :])           # (B, n_out) fp64
+        if not fp64:
+            total_all = total_all.float()
+        lfnull = lfnull64.float()
+
+        phi_full = t.zeros(b, self.n_groups, self.n_out, device=self.device,
+                           dtype=t.float64 if fp64 else t.float32)
 
         # bucket instances by varying-group pattern (benchmark case: 1 bucket)
         if self.n_groups <= 62:
@@ -1322,6 +1454,28 @@ class GpuKernelShap:
                 continue
             plan = self.engine._plan(m, nsamples)
             gids = ids + instance_offset
+            if not fp64 and self._packed_ok(m, plan, l1_reg):
+                # same four kernels as the captured graph body
+                nb = len(ids)
+                gid0 = int(gids[0])
+                if np.array_equal(gids, np.arange(gid0, gid0 + nb)):
+                    ids32 = t.arange(gid0, gid0 + nb, dtype=t.int32,
+                                     device=self.device)
+                else:
+                    ids32 = t.tensor(gids.astype(np.int32), device=self.device)
+                vidx_t = t.tensor(varying, dtype=t.int64, device=self.device)
+                if nb == b:
+                    self._packed_pipeline(
+                        X_dev.contiguous(), plan, vidx_t, ids32, phi_full,
+                        timer=timer)
+                else:
+                    phi_sub = self._buf(
+                        "phip", (nb, self.n_groups, self.n_out))
+                    self._packed_pipeline(
+                        X_dev[ids_t], plan, vidx_t, ids32, phi_sub,
+                        timer=timer)
+                    phi_full[ids_t] = phi_sub
+                continue
             masks, kw = self._device_masks(plan, gids)
             timer.mark("masks")
             sub_X = X_dev[ids_t]

@@ -68,6 +68,29 @@ extern "C" int launch_fused_predict_tiled_bf16(
     const float* wbg, float* partial, float* ey, int B, int S, int M,
     int Mpad, int Npad, int n_out, int act, int split, hipStream_t stream);
 
+// packed linear pipeline
+extern "C" int launch_fill_masks_packed(
+    uint64_t* packed, const uint64_t* enum_packed, int B, int S, int M, int ne,
+    int n_random, const float* cdf, const int* sizes, int n_sizes,
+    int num_paired, uint32_t seed, const int32_t* inst_ids, hipStream_t stream);
+
+extern "C" int launch_linear_prepare(
+    const float* X, const float* W, const float* bias,
+    const int64_t* col_group, const int64_t* vidx, const float* bgp,
+    const double* lfnull64, float* diff, float* total, int B, int D, int G,
+    int N, int m, int Mpad, int Npad, int n_out, int act, int link,
+    hipStream_t stream);
+
+extern "C" int launch_fused_predict_linear_packed(
+    const uint64_t* packed, const float* diff, const float* base,
+    const float* wbg, const float* lfnull, float* ey, int B, int S, int Mpad,
+    int Npad, int n_out, int act, int link, hipStream_t stream);
+
+extern "C" int launch_wls_solve_packed(
+    const uint64_t* packed, const float* kw, const float* ey_adj,
+    const float* total, const int64_t* vidx, float* phi_full, int B, int S,
+    int M, int n_out, int G, hipStream_t stream);
+
 // mlp_kernels.hip
 extern "C" int launch_fused_predict_mlp(
     const uint8_t* masks, const void* xp1, const void* bgp1n,
@@ -201,6 +224,126 @@ void pack_masks(torch::Tensor masks, torch::Tensor packed) {
         masks.data_ptr<uint8_t>(),
         reinterpret_cast<uint64_t*>(packed.data_ptr<int64_t>()),
         B, S, M, current_stream());
+}
+
+#define CHECK_F32(t) TORCH_CHECK((t).dtype() == torch::kFloat32, #t " must be float32")
+#define CHECK_I64(t) TORCH_CHECK((t).dtype() == torch::kInt64, #t " must be int64")
+
+void fill_masks_packed(
+    torch::Tensor packed, torch::Tensor enum_packed, int64_t n_random,
+    torch::Tensor cdf, torch::Tensor sizes, int64_t num_paired, int64_t seed,
+    torch::Tensor inst_ids, int64_t M) {
+    CHECK_DEV(packed); CHECK_DEV(enum_packed); CHECK_DEV(cdf); CHECK_DEV(sizes);
+    CHECK_DEV(inst_ids);
+    CHECK_I64(packed); CHECK_I64(enum_packed); CHECK_F32(cdf);
+    TORCH_CHECK(sizes.dtype() == torch::kInt32, "sizes must be int32");
+    TORCH_CHECK(inst_ids.dtype() == torch::kInt32, "inst_ids must be int32");
+    TORCH_CHECK(packed.dim() == 2 && enum_packed.dim() == 1,
+                "packed must be (B,S), enum_packed (ne,)");
+    int B = packed.size(0), S = packed.size(1), ne = enum_packed.size(0);
+    TORCH_CHECK(inst_ids.dim() == 1 && inst_ids.size(0) == B, "inst_ids length");
+    TORCH_CHECK(n_random >= 0 && ne + n_random == S, "ne + n_random must equal S");
+    TORCH_CHECK(cdf.dim() == 1 && sizes.dim() == 1
+                && cdf.size(0) == sizes.size(0), "cdf vs sizes");
+    TORCH_CHECK(n_random == 0 || cdf.size(0) >= 1, "empty size table");
+    int rc = launch_fill_masks_packed(
+        reinterpret_cast<uint64_t*>(packed.data_ptr<int64_t>()),
+        reinterpret_cast<const uint64_t*>(enum_packed.data_ptr<int64_t>()),
+        B, S, (int)M, ne, (int)n_random, cdf.data_ptr<float>(),
+        sizes.data_ptr<int>(), (int)cdf.size(0), (int)num_paired,
+        (uint32_t)seed, inst_ids.data_ptr<int32_t>(), current_stream());
+    TORCH_CHECK(rc == 0, "fill_masks_packed: unsupported shape (1<=M<=64)");
+}
+
+void linear_prepare(
+    torch::Tensor X, torch::Tensor W, torch::Tensor bias,
+    torch::Tensor col_group, torch::Tensor vidx, torch::Tensor bgp,
+    torch::Tensor lfnull64, torch::Tensor diff, torch::Tensor total,
+    int64_t act, int64_t link) {
+    CHECK_DEV(X); CHECK_DEV(W); CHECK_DEV(bias); CHECK_DEV(col_group);
+    CHECK_DEV(vidx); CHECK_DEV(bgp); CHECK_DEV(lfnull64); CHECK_DEV(diff);
+    CHECK_DEV(total);
+    CHECK_F32(X); CHECK_F32(W); CHECK_F32(bias); CHECK_F32(bgp); CHECK_F32(diff);
+    CHECK_F32(total); CHECK_I64(col_group); CHECK_I64(vidx);
+    TORCH_CHECK(lfnull64.dtype() == torch::kFloat64, "lfnull64 must be float64");
+    TORCH_CHECK(X.dim() == 2 && W.dim() == 2 && bgp.dim() == 3 && diff.dim() == 4
+                && total.dim() == 2 && vidx.dim() == 1, "operand ranks");
+    int B = X.size(0), D = X.size(1), n_out = W.size(0);
+    int N = bgp.size(0), G = bgp.size(1), OI = bgp.size(2), m = vidx.size(0);
+    int Mpad = diff.size(2), Npad = diff.size(3);
+    TORCH_CHECK(W.size(1) == D && bias.numel() == n_out
+                && col_group.numel() == D && lfnull64.numel() == n_out,
+                "W (n_out,D), b (n_out), col_group (D), lfnull64 (n_out)");
+    TORCH_CHECK(OI == (act == 3 ? 1 : n_out), "background image count vs act");
+    TORCH_CHECK(diff.size(0) == B && diff.size(1) == OI, "diff (B,OI,Mpad,Npad)");
+    TORCH_CHECK(total.size(0) == B && total.size(1) == n_out, "total (B,n_out)");
+    TORCH_CHECK(link == 0 || link == 1, "link must be 0 or 1");
+    int rc = launch_linear_prepare(
+        X.data_ptr<float>(), W.data_ptr<float>(), bias.data_ptr<float>(),
+        col_group.data_ptr<int64_t>(), vidx.data_ptr<int64_t>(),
+        bgp.data_ptr<float>(), lfnull64.data_ptr<double>(),
+        diff.data_ptr<float>(), total.data_ptr<float>(), B, D, G, N, m, Mpad,
+        Npad, n_out, (int)act, (int)link, current_stream());
+    TORCH_CHECK(rc == 0, "linear_prepare: unsupported shape (m<=Mpad, m<=64, "
+                         "N<=Npad, n_out<=8, act 3 needs n_out==2)");
+}
+
+void fused_predict_linear_packed(
+    torch::Tensor packed, torch::Tensor diff, torch::Tensor base,
+    torch::Tensor wbg, torch::Tensor ey, int64_t act, int64_t link,
+    c10::optional<torch::Tensor> lfnull) {
+    CHECK_DEV(packed); CHECK_DEV(diff); CHECK_DEV(base); CHECK_DEV(wbg); CHECK_DEV(ey);
+    CHECK_I64(packed); CHECK_F32(diff); CHECK_F32(base); CHECK_F32(wbg); CHECK_F32(ey);
+    TORCH_CHECK(packed.dim() == 2 && diff.dim() == 4 && ey.dim() == 3
+                && base.dim() == 2, "operand ranks");
+    int B = packed.size(0), S = packed.size(1);
+    int Mpad = diff.size(2), Npad = diff.size(3);
+    int n_out = ey.size(2);
+    int oimg = (act == 3) ? 1 : n_out;
+    TORCH_CHECK(diff.size(0) == B && diff.size(1) == oimg, "diff (B,oimg,Mpad,Npad) vs act");
+    TORCH_CHECK(ey.size(0) == B && ey.size(1) == S, "ey shape");
+    TORCH_CHECK(base.size(0) == oimg && base.size(1) == Npad, "base shape");
+    TORCH_CHECK(wbg.numel() == Npad, "wbg shape");
+    const float* lf = nullptr;
+    if (lfnull.has_value()) {
+        CHECK_DEV(lfnull.value()); CHECK_F32(lfnull.value());
+        TORCH_CHECK(lfnull->numel() == n_out, "lfnull must be (n_out,)");
+        lf = lfnull->data_ptr<float>();
+    }
+    TORCH_CHECK(link == 0 || (link == 1 && lf != nullptr),
+                "link must be 0, or 1 with lfnull given");
+    int rc = launch_fused_predict_linear_packed(
+        reinterpret_cast<const uint64_t*>(packed.data_ptr<int64_t>()),
+        diff.data_ptr<float>(), base.data_ptr<float>(), wbg.data_ptr<float>(),
+        lf, ey.data_ptr<float>(), B, S, Mpad, Npad, n_out, (int)act, (int)link,
+        current_stream());
+    TORCH_CHECK(rc == 0, "fused_predict_linear_packed: unsupported shape "
+                         "(Mpad%4==0, Mpad<=64, Npad%16==0, Npad<=128, n_out in "
+                         "{1,2,4}, operand images within 64 KiB of LDS)");
+}
+
+void wls_solve_packed(
+    torch::Tensor packed, torch::Tensor kw, torch::Tensor ey_adj,
+    torch::Tensor total, torch::Tensor vidx, torch::Tensor phi_full) {
+    CHECK_DEV(packed); CHECK_DEV(kw); CHECK_DEV(ey_adj); CHECK_DEV(total);
+    CHECK_DEV(vidx); CHECK_DEV(phi_full);
+    CHECK_I64(packed); CHECK_F32(kw); CHECK_F32(ey_adj); CHECK_F32(total);
+    CHECK_I64(vidx); CHECK_F32(phi_full);
+    TORCH_CHECK(packed.dim() == 2 && ey_adj.dim() == 3 && phi_full.dim() == 3
+                && vidx.dim() == 1 && total.dim() == 2, "operand ranks");
+    int B = packed.size(0), S = packed.size(1), M = vidx.size(0);
+    int n_out = ey_adj.size(2), G = phi_full.size(1);
+    TORCH_CHECK(kw.numel() == S, "kw must be (S,)");
+    TORCH_CHECK(ey_adj.size(0) == B && ey_adj.size(1) == S, "ey_adj shape");
+    TORCH_CHECK(total.size(0) == B && total.size(1) == n_out, "total shape");
+    TORCH_CHECK(phi_full.size(0) == B && phi_full.size(2) == n_out, "phi_full shape");
+    int rc = launch_wls_solve_packed(
+        reinterpret_cast<const uint64_t*>(packed.data_ptr<int64_t>()),
+        kw.data_ptr<float>(), ey_adj.data_ptr<float>(), total.data_ptr<float>(),
+        vidx.data_ptr<int64_t>(), phi_full.data_ptr<float>(), B, S, M, n_out,
+        G, current_stream());
+    TORCH_CHECK(rc == 0, "wls_solve_packed: unsupported shape (2<=M<=G, "
+                         "(M-1)+n_out<=16)");
 }
 
 void fused_predict_bf16(
@@ -626,6 +769,34 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("hidden_b"), pybind11::arg("wout"),
           pybind11::arg("bout"), pybind11::arg("wbg"), pybind11::arg("ey"),
           pybind11::arg("act"), pybind11::arg("hidden_act") = 0);
+    m.def("fill_masks_packed", &fill_masks_packed,
+          "Philox coalition sampling straight into packed u64 words (K2p): "
+          "bit-identical to the enumerated-row copy, fill_random_masks and "
+          "pack_masks in sequence, M <= 64",
+          pybind11::arg("packed"), pybind11::arg("enum_packed"),
+          pybind11::arg("n_random"), pybind11::arg("cdf"),
+          pybind11::arg("sizes"), pybind11::arg("num_paired"),
+          pybind11::arg("seed"), pybind11::arg("inst_ids"), pybind11::arg("M"));
+    m.def("linear_prepare", &linear_prepare,
+          "per-call operand prep for the packed linear pipeline (K0p): diff "
+          "image in the build_diff_f32 layout plus the fp64-evaluated totals",
+          pybind11::arg("X"), pybind11::arg("W"), pybind11::arg("b"),
+          pybind11::arg("col_group"), pybind11::arg("vidx"),
+          pybind11::arg("bgp"), pybind11::arg("lfnull64"),
+          pybind11::arg("diff"), pybind11::arg("total"), pybind11::arg("act"),
+          pybind11::arg("link"));
+    m.def("fused_predict_linear_packed", &fused_predict_linear_packed,
+          "MFMA fused predict from packed mask words with the link fused into "
+          "the epilogue (K3p)",
+          pybind11::arg("packed"), pybind11::arg("diff"), pybind11::arg("base"),
+          pybind11::arg("wbg"), pybind11::arg("ey"), pybind11::arg("act"),
+          pybind11::arg("link") = 0, pybind11::arg("lfnull") = pybind11::none());
+    m.def("wls_solve_packed", &wls_solve_packed,
+          "MFMA WLS solve with (S,) kernel weights, scattered into "
+          "phi_full (B,G,n_out) through vidx (K7p)",
+          pybind11::arg("packed"), pybind11::arg("kw"), pybind11::arg("ey_adj"),
+          pybind11::arg("total"), pybind11::arg("vidx"),
+          pybind11::arg("phi_full"));
     m.def("fill_random_masks", &fill_random_masks,
           "Philox coalition sampling (K2)");
     m.def("fused_predict_linear", &fused_predict_linear,

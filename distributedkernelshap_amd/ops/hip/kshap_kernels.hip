@@ -2170,3 +2170,700 @@ extern "C" int launch_fused_predict_tiled(
     }
     return 0;
 }
+
+// ========================================================================= //
+// Packed linear pipeline (M <= 64): the whole step runs from the (B,S) u64
+// mask words in four kernels —
+//   K2p fill_masks_packed            sampler that emits the words only
+//   K0p linear_prepare               diff image + per-instance totals
+//   K3p fused_predict_linear_packed  predict from the words, link fused
+//   K7p wls_solve_packed             (S,) weights, scatter into phi_full
+// The u8 mask tensor, the (B,S) weight broadcast and the elementwise link
+// passes over ey do not exist on this path.
+// ========================================================================= //
+
+// K2p: same Philox keying, chunking and pair layout as
+// fill_random_masks_kernel<1>; each row is stored as the u64 the sampler
+// already holds (and its complement masked to M bits).  Rows [0, ne) of every
+// instance receive the instance-independent enumerated words.
+__global__ void fill_masks_packed_kernel(
+    uint64_t* __restrict__ packed,         // (B, S)
+    const uint64_t* __restrict__ enum_packed,  // (ne,)
+    int B, int S, int M, int ne, int n_random,
+    const float* __restrict__ cdf, const int* __restrict__ sizes, int n_sizes,
+    int num_paired, uint32_t seed, const int32_t* __restrict__ inst_ids,
+    int n_chunks)
+{
+    const int nblk = n_chunks / 8;
+    const int b = blockIdx.x / nblk;
+    const int cb = blockIdx.x % nblk;
+    if (b >= B) return;
+    uint64_t* prow = packed + (size_t)b * S;
+    // enumerated rows: coalesced 8-byte broadcast, split over the instance's
+    // blocks
+    for (int i = cb * blockDim.x + threadIdx.x; i < ne; i += nblk * blockDim.x)
+        prow[i] = enum_packed[i];
+
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int chunk_id = cb * 8 + (threadIdx.x >> 6);
+    const int chunk = (n_random + n_chunks - 1) / n_chunks;
+    const int lo = chunk_id * chunk;
+    const int hi = min(lo + chunk, n_random);
+    if (lo >= hi) return;
+    const uint64_t mmask = M >= 64 ? ~0ull : ((1ull << M) - 1ull);
+
+    int remaining = hi - lo;
+    int written = lo;
+    uint32_t iter = 0;
+    while (remaining > 0) {
+        Philox rng;
+        rng.init(seed, (uint32_t)inst_ids[b], iter,
+                 (uint32_t)(chunk_id * WAVE + lane) | 0x52000000u);
+        float u = (rng.next_u32() >> 8) * (1.0f / 16777216.0f);
+        int si = 0;
+        while (si < n_sizes - 1 && u > cdf[si]) ++si;
+        int ssize = sizes[si];
+        bool paired = ssize <= num_paired;
+
+        uint64_t pairmask = __ballot(paired);
+        uint64_t below = pairmask & ((1ull << lane) - 1ull);
+        int rows_before = lane + __popcll(below);
+        int total_rows = WAVE + __popcll(pairmask);
+
+        if (rows_before < remaining) {
+            uint64_t bits = 0ull;
+            int got = 0;
+            int guard = 0;
+            while (got < ssize && guard < 65536) {
+                uint32_t r = rng.next_below((uint32_t)M);
+                uint64_t bit = 1ull << (r & 63);
+                if (!(bits & bit)) { bits |= bit; ++got; }
+                ++guard;
+            }
+            uint64_t* row = prow + ne + written + rows_before;
+            row[0] = bits;
+            if (paired && rows_before + 1 < remaining) row[1] = ~bits & mmask;
+        }
+        int consumed = total_rows < remaining ? total_rows : remaining;
+        written += consumed;
+        remaining -= consumed;
+        ++iter;
+    }
+}
+
+extern "C" int launch_fill_masks_packed(
+    uint64_t* packed, const uint64_t* enum_packed, int B, int S, int M, int ne,
+    int n_random, const float* cdf, const int* sizes, int n_sizes,
+    int num_paired, uint32_t seed, const int32_t* inst_ids, hipStream_t stream)
+{
+    if (M < 1 || M > 64 || ne < 0 || n_random < 0 || ne + n_random != S)
+        return -1;
+    if (B <= 0 || S <= 0) return 0;
+    const int n_chunks = kshap_sampler_chunks(n_random);
+    fill_masks_packed_kernel<<<dim3(B * (n_chunks / 8)), dim3(8 * WAVE), 0,
+                               stream>>>(
+        packed, enum_packed, B, S, M, ne, n_random, cdf, sizes, n_sizes,
+        num_paired, seed, inst_ids, n_chunks);
+    return 0;
+}
+
+// K0p: per-call operand prep, one workgroup per instance.
+//   x_part[k,o] = sum_{j in group vidx[k]} x[j] * W[o,j]   (fp32, j ascending)
+//   diff[b,oi,k,n] = xpi[k,oi] - bgp[n, vidx[k], oi]       (pad slots 0)
+//   total[b,o] = link(act(x W^T + b)) - lfnull64[o]        (fp64, then cast)
+// img3: the operand image is the class-1 minus class-0 logit difference
+// (binary softmax, one image for two outputs).
+#define PREP_MAX_M 64
+#define PREP_MAX_NOUT 8
+
+__global__ __launch_bounds__(256)
+void linear_prepare_kernel(
+    const float* __restrict__ X,          // (B, D)
+    const float* __restrict__ W,          // (n_out, D)
+    const float* __restrict__ bias,       // (n_out,)
+    const int64_t* __restrict__ col_group,  // (D,)
+    const int64_t* __restrict__ vidx,     // (m,)
+    const float* __restrict__ bgp,        // (N, G, OI)
+    const double* __restrict__ lfnull64,  // (n_out,)
+    float* __restrict__ diff,             // (B, OI, Mpad, Npad)
+    float* __restrict__ total,            // (B, n_out)
+    int D, int G, int N, int m, int Mpad, int Npad, int n_out, int OI,
+    int act, int link)
+{
+    const int b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const bool img3 = act == 3;
+    if (img3) act = 2;                    // the totals see the plain softmax
+    __shared__ float xp_s[PREP_MAX_M * PREP_MAX_NOUT];
+    __shared__ float xpi_s[PREP_MAX_M * PREP_MAX_NOUT];
+    __shared__ int g_s[PREP_MAX_M];
+    __shared__ double z_s[PREP_MAX_NOUT];
+    const float* x = X + (size_t)b * D;
+
+    if (tid < m) g_s[tid] = (int)vidx[tid];
+    for (int p = tid; p < m * n_out; p += 256) {
+        const int k = p / n_out, o = p % n_out;
+        const int64_t g = vidx[k];
+        const float* w = W + (size_t)o * D;
+        // unconditional loads (several in flight per thread); columns of
+        // other groups add an exact 0
+        float acc = 0.0f;
+#pragma unroll 8
+        for (int j = 0; j < D; ++j) {
+            const float t = __fmul_rn(x[j], w[j]);
+            acc = __fadd_rn(acc, col_group[j] == g ? t : 0.0f);
+        }
+        xp_s[p] = acc;
+    }
+    // fp64 logits for the totals: the last n_out threads, so they overlap the
+    // group sums above
+    if (tid >= 256 - n_out) {
+        const int o = tid - (256 - n_out);
+        const float* w = W + (size_t)o * D;
+        double z = (double)bias[o];
+#pragma unroll 8
+        for (int j = 0; j < D; ++j) z += (double)x[j] * (double)w[j];
+        z_s[o] = z;
+    }
+    __syncthreads();
+    for (int p = tid; p < m * OI; p += 256) {
+        const int k = p / OI, oi = p % OI;
+        xpi_s[p] = img3 ? __fsub_rn(xp_s[k * n_out + 1], xp_s[k * n_out])
+                        : xp_s[k * n_out + oi];
+    }
+    if (tid < n_out) {
+        const int o = tid;
+        double p;
+        if (act == 1) {
+            p = 1.0 / (1.0 + exp(-z_s[o]));
+        } else if (act == 2) {
+            double mx = z_s[0];
+            for (int q = 1; q < n_out; ++q) mx = fmax(mx, z_s[q]);
+            double sum = 0.0;
+            for (int q = 0; q < n_out; ++q) sum += exp(z_s[q] - mx);
+            p = exp(z_s[o] - mx) / sum;
+        } else {
+            p = z_s[o];
+        }
+        if (link) {
+            p = fmin(fmax(p, 1e-15), 1.0 - 1e-15);
+            p = log(p / (1.0 - p));
+        }
+        total[(size_t)b * n_out + o] = (float)(p - lfnull64[o]);
+    }
+    __syncthreads();
+    float* dout = diff + (size_t)b * OI * Mpad * Npad;
+    const int per_img = Mpad * Npad;
+    for (int idx = tid; idx < OI * per_img; idx += 256) {
+        const int n = idx % Npad;
+        const int k = (idx / Npad) % Mpad;
+        const int oi = idx / per_img;
+        float v = 0.0f;
+        if (k < m && n < N && g_s[k] >= 0 && g_s[k] < G)
+            v = __fsub_rn(xpi_s[k * OI + oi],
+                          bgp[((size_t)n * G + g_s[k]) * OI + oi]);
+        dout[idx] = v;
+    }
+}
+
+extern "C" int launch_linear_prepare(
+    const float* X, const float* W, const float* bias,
+    const int64_t* col_group, const int64_t* vidx, const float* bgp,
+    const double* lfnull64, float* diff, float* total, int B, int D, int G,
+    int N, int m, int Mpad, int Npad, int n_out, int act, int link,
+    hipStream_t stream)
+{
+    if (m < 1 || m > PREP_MAX_M || m > Mpad || N > Npad || n_out < 1
+            || n_out > PREP_MAX_NOUT || act < 0 || act > 3)
+        return -1;
+    if (act == 3 && n_out != 2) return -1;
+    const int OI = act == 3 ? 1 : n_out;
+    if (B <= 0) return 0;
+    linear_prepare_kernel<<<dim3(B), dim3(256), 0, stream>>>(
+        X, W, bias, col_group, vidx, bgp, lfnull64, diff, total, D, G, N, m,
+        Mpad, Npad, n_out, OI, act, link);
+    return 0;
+}
+
+// K3p: fused predict from the packed words.  Same tiling and MFMA maths as
+// fused_predict_linear_kernel; what differs:
+//   * the A operand is one 8-byte load per lane per 64-row sub-tile (the
+//     next sub-tile's word is requested before this one's epilogue);
+//     a_k = bit (4*ks + lane>>4) of the word, a bit-field extract + convert
+//   * KS = Mpad/4 k-steps unrolled at compile time (KS 1..4); KS == 0 is
+//     the runtime loop for Mpad up to 64
+//   * accumulators start from base[n], so the epilogue has no add; for the
+//     sigmoid-type activations (ACT 1 and 3) diff and base are scaled by
+//     -log2(e) while staged into LDS, leaving v_exp, 1+, v_rcp, fma per value
+//   * the row sums are reduced with DPP adds, and lanes 0..3 of each 16-lane
+//     group apply the optional link and store one row's outputs each as a
+//     single vector store
+// link: 0 = ey - lfnull (or plain ey when lfnull is null), 1 = logit(clamp(
+// ey, 1e-7, 1-1e-7)) - lfnull with the logit as ln2*(log2 p - log2(1-p)) on
+// the hardware log (absolute error ~1e-7 * |log|).
+
+__device__ __forceinline__ float dpp_add_quad1(float v) {   // + lane^1
+    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
+        0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float dpp_add_quad2(float v) {   // + lane^2
+    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
+        0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float dpp_add_half_mirror(float v) {  // 8-lane mirror
+    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
+        0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float dpp_add_mirror(float v) {  // 16-lane mirror
+    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
+        0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
+}
+
+template <int NOUT, int ACT, int NT, int KS>
+__global__ __launch_bounds__(256, 2)   // <= 256 registers: the accumulators
+void fused_predict_linear_packed_kernel(  // stay in VGPRs the VALU can read
+    const uint64_t* __restrict__ packed, // (B, S) mask words
+    const float* __restrict__ diff,      // (B, OIMG, Mpad, NT*16)
+    const float* __restrict__ base,      // (OIMG, NT*16)
+    const float* __restrict__ wbg,       // (NT*16)  0 for padding cols
+    const float* __restrict__ lfnull,    // (NOUT,) or null
+    float* __restrict__ ey,              // (B, S, NOUT)
+    int B, int S, int Mpad_rt, int link)
+{
+    constexpr int OIMG = (ACT == 3) ? 1 : NOUT;
+    constexpr int NACC = (ACT == 3) ? 1 : NOUT;
+    constexpr int NPAD = NT * 16;
+    constexpr int NSTRIDE = NPAD + ((16 - (NPAD & 31)) & 31);  // ≡16 mod 32
+    constexpr bool SIG = (ACT == 1 || ACT == 3);
+    // accumulator tiles beyond 16 are processed in two column halves (as in
+    // the u8 kernel) to bound the AGPR footprint
+    constexpr int NHALF = (NT * OIMG > 16) ? 2 : 1;
+    constexpr int NTH = (NT + NHALF - 1) / NHALF;
+    const int Mpad = KS > 0 ? KS * 4 : Mpad_rt;
+    const int n_stiles = (S + S_TILE - 1) / S_TILE;
+    const int b = blockIdx.x / n_stiles;
+    const int stile = blockIdx.x % n_stiles;
+    const int s0 = stile * S_TILE;
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wave = tid >> 6;
+
+    extern __shared__ float lds[];
+    float* diff_lds = lds;                                   // OIMG*Mpad*NSTRIDE
+    float* base_lds = diff_lds + OIMG * Mpad * NSTRIDE;      // OIMG*NPAD
+    float* wbg_lds = base_lds + OIMG * NPAD;                 // NPAD
+
+    const float scale = SIG ? -1.44269504088896340736f : 1.0f;
+    const float* dsrc = diff + (size_t)b * OIMG * Mpad * NPAD;
+    for (int idx = tid; idx < OIMG * Mpad * NPAD; idx += 256) {
+        int ok = idx / NPAD;             // o * Mpad + k
+        int n = idx % NPAD;
+        diff_lds[ok * NSTRIDE + n] = dsrc[idx] * scale;
+    }
+    for (int idx = tid; idx < OIMG * NPAD; idx += 256)
+        base_lds[idx] = base[idx] * scale;
+    for (int idx = tid; idx < NPAD; idx += 256) wbg_lds[idx] = wbg[idx];
+    __syncthreads();
+
+    const int swave = wave * 16;
+    const int arow = lane & 15;
+    const int akcol = lane >> 4;
+    const float* dbase = diff_lds + akcol * NSTRIDE + arow;
+    const uint64_t* plane = packed + (size_t)b * S;
+
+    // the word loads are unconditional (row index clamped into the instance)
+    // and validity is applied where the word is consumed, one iteration
+    // later, so no wait sits between a prefetch and the epilogue
+    int srow = s0 + swave + arow;
+    uint64_t bits_next = plane[min(srow, S - 1)];
+
+    for (int sub = 0; sub < S_TILE / S_SUB; ++sub) {
+        const int ssub0 = s0 + sub * S_SUB;
+        if (ssub0 >= S) break;
+        // bit (4*ks) of w is this lane's A element of k-step ks; rows past S
+        // carry an all-zero word
+        const uint64_t w = (srow < S ? bits_next : 0ull) >> akcol;
+        srow += S_SUB;
+        bits_next = plane[min(srow, S - 1)];
+
+        float partial[NACC][4];
+#pragma unroll
+        for (int o = 0; o < NACC; ++o)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) partial[o][r] = 0.0f;
+
+#pragma unroll
+        for (int half = 0; half < NHALF; ++half) {
+        const int CT0 = half * NTH;
+        const int CTN = half == 0 ? NTH : NT - NTH;
+
+        f32x4 acc[NTH][OIMG];
+#pragma unroll
+        for (int ct = 0; ct < NTH; ++ct)
+#pragma unroll
+            for (int o = 0; o < OIMG; ++o) {
+                const float b0 =
+                    ct < CTN ? base_lds[o * NPAD + (CT0 + ct) * 16 + arow] : 0.0f;
+                acc[ct][o] = (f32x4){b0, b0, b0, b0};
+            }
+
+        if constexpr (KS > 0) {
+            const uint32_t wlo = (uint32_t)w;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const float a = (float)((wlo >> (4 * ks)) & 1u);
+#pragma unroll
+                for (int ct = 0; ct < NTH; ++ct) {
+                    if (ct < CTN) {
+#pragma unroll
+                        for (int o = 0; o < OIMG; ++o) {
+                            float bv = dbase[(o * (KS * 4) + ks * 4) * NSTRIDE + (CT0 + ct) * 16];
+                            acc[ct][o] =
+                                __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc[ct][o], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+        } else {
+            uint64_t wk = w;
+            for (int ks = 0; ks < Mpad; ks += 4) {
+                const float a = (float)((uint32_t)wk & 1u);
+                wk >>= 4;
+#pragma unroll
+                for (int ct = 0; ct < NTH; ++ct) {
+                    if (ct < CTN) {
+#pragma unroll
+                        for (int o = 0; o < OIMG; ++o) {
+                            float bv = dbase[(o * Mpad + ks) * NSTRIDE + (CT0 + ct) * 16];
+                            acc[ct][o] =
+                                __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc[ct][o], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+        }
+
+        // ---- epilogue: activation + weighted reduction over n -------------
+        // C/D map: col = lane&15, row = (lane>>4)*4 + reg
+#pragma unroll
+        for (int ct = 0; ct < NTH; ++ct) {
+            if (ct >= CTN) break;
+            const float wn = wbg_lds[(CT0 + ct) * 16 + arow];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float zz[NACC];
+                if (SIG) {
+                    // acc holds -log2(e) * z
+#pragma unroll
+                    for (int o = 0; o < NACC; ++o)
+                        zz[o] = fast_rcp(1.0f + __builtin_amdgcn_exp2f(acc[ct][o][r]));
+                } else if (ACT == 2 && NOUT == 2) {
+                    float p1 = fast_rcp(1.0f + __expf(acc[ct][0][r] - acc[ct][1][r]));
+                    zz[0] = 1.0f - p1;
+                    zz[NACC - 1] = p1;
+                } else if (ACT == 2) {
+                    float mx = acc[ct][0][r];
+#pragma unroll
+                    for (int o = 1; o < NACC; ++o) mx = fmaxf(mx, acc[ct][o][r]);
+                    float sum = 0.0f;
+#pragma unroll
+                    for (int o = 0; o < NACC; ++o) { zz[o] = __expf(acc[ct][o][r] - mx); sum += zz[o]; }
+                    float inv = fast_rcp(sum);
+#pragma unroll
+                    for (int o = 0; o < NACC; ++o) zz[o] *= inv;
+                } else {
+#pragma unroll
+                    for (int o = 0; o < NACC; ++o) zz[o] = acc[ct][o][r];
+                }
+#pragma unroll
+                for (int o = 0; o < NACC; ++o) partial[o][r] += wn * zz[o];
+            }
+        }
+        }  // half loop
+
+        // reduce over the 16 lanes of each row group; afterwards every lane
+        // of the group holds the four row sums
+#pragma unroll
+        for (int o = 0; o < NACC; ++o)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = partial[o][r];
+                v = dpp_add_quad1(v);
+                v = dpp_add_quad2(v);
+                v = dpp_add_half_mirror(v);
+                v = dpp_add_mirror(v);
+                partial[o][r] = v;
+            }
+        // lane arow < 4 of each group owns row arow of the group's four
+        const int ss = ssub0 + swave + akcol * 4 + arow;
+        if (arow < 4 && ss < S) {
+            float out[NOUT];
+            if (ACT == 3) {
+                const float p1 = arow == 0 ? partial[0][0] : arow == 1 ? partial[0][1]
+                               : arow == 2 ? partial[0][2] : partial[0][3];
+                out[0] = 1.0f - p1;
+                out[NOUT - 1] = p1;
+            } else {
+#pragma unroll
+                for (int o = 0; o < NACC; ++o)
+                    out[o] = arow == 0 ? partial[o][0] : arow == 1 ? partial[o][1]
+                           : arow == 2 ? partial[o][2] : partial[o][3];
+            }
+            if (link == 1) {
+#pragma unroll
+                for (int o = 0; o < NOUT; ++o) {
+                    const float p = fminf(fmaxf(out[o], 1e-7f), 0.9999999f);
+                    out[o] = 0.69314718055994530942f
+                        * (__builtin_amdgcn_logf(p) - __builtin_amdgcn_logf(1.0f - p));
+                }
+            }
+            if (lfnull != nullptr) {
+#pragma unroll
+                for (int o = 0; o < NOUT; ++o) out[o] -= lfnull[o];
+            }
+            float* dst = ey + ((size_t)b * S + ss) * NOUT;
+            if constexpr (NOUT == 2) {
+                *(float2*)dst = make_float2(out[0], out[1]);
+            } else if constexpr (NOUT == 4) {
+                *(float4*)dst = make_float4(out[0], out[1], out[2], out[3]);
+            } else {
+                dst[0] = out[0];
+            }
+        }
+    }  // sub-tile loop
+}
+
+template <int NOUT, int ACT, int NT>
+static int launch_fpp_ks(
+    const uint64_t* packed, const float* diff, const float* base,
+    const float* wbg, const float* lfnull, float* ey, int B, int S, int Mpad,
+    int link, hipStream_t stream)
+{
+    const int n_stiles = (S + S_TILE - 1) / S_TILE;
+    dim3 grid(B * n_stiles), block(256);
+    constexpr int NPAD = NT * 16;
+    constexpr int NSTRIDE = NPAD + ((16 - (NPAD & 31)) & 31);
+    constexpr int OIMG = (ACT == 3) ? 1 : NOUT;
+    const size_t lds = (size_t)(OIMG * Mpad * NSTRIDE + OIMG * NPAD + NPAD) * 4;
+    if (lds > 64 * 1024) return -1;
+#define KSHAP_FPP(KSV) \
+    fused_predict_linear_packed_kernel<NOUT, ACT, NT, KSV> \
+        <<<grid, block, lds, stream>>>(packed, diff, base, wbg, lfnull, ey, \
+                                       B, S, Mpad, link)
+    // compile-time k-steps for the sigmoid-type activations (the shapes the
+    // step time is spent in); everything else takes the runtime loop
+    if constexpr (ACT == 1 || ACT == 3) {
+        switch (Mpad / 4) {
+            case 1: KSHAP_FPP(1); return 0;
+            case 2: KSHAP_FPP(2); return 0;
+            case 3: KSHAP_FPP(3); return 0;
+            case 4: KSHAP_FPP(4); return 0;
+            default: break;
+        }
+    }
+    KSHAP_FPP(0);
+#undef KSHAP_FPP
+    return 0;
+}
+
+template <int NOUT, int ACT>
+static int launch_fpp_nt(
+    const uint64_t* packed, const float* diff, const float* base,
+    const float* wbg, const float* lfnull, float* ey, int B, int S, int Mpad,
+    int Npad, int link, hipStream_t stream)
+{
+#define KSHAP_FPP_NT(NTV) \
+    case NTV: \
+        return launch_fpp_ks<NOUT, ACT, NTV>(packed, diff, base, wbg, lfnull, \
+                                             ey, B, S, Mpad, link, stream);
+    switch (Npad / 16) {
+        KSHAP_FPP_NT(1) KSHAP_FPP_NT(2) KSHAP_FPP_NT(3) KSHAP_FPP_NT(4)
+        KSHAP_FPP_NT(5) KSHAP_FPP_NT(6) KSHAP_FPP_NT(7) KSHAP_FPP_NT(8)
+    }
+#undef KSHAP_FPP_NT
+    return -1;
+}
+
+template <int NOUT>
+static int launch_fpp_act(
+    const uint64_t* packed, const float* diff, const float* base,
+    const float* wbg, const float* lfnull, float* ey, int B, int S, int Mpad,
+    int Npad, int act, int link, hipStream_t stream)
+{
+    switch (act) {
+        case 0:
+            return launch_fpp_nt<NOUT, 0>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, link, stream);
+        case 1:
+            return launch_fpp_nt<NOUT, 1>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, link, stream);
+        case 2:
+            return launch_fpp_nt<NOUT, 2>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, link, stream);
+        case 3:
+            if constexpr (NOUT == 2)
+                return launch_fpp_nt<NOUT, 3>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, link, stream);
+            return -1;
+        default:
+            return -1;
+    }
+}
+
+extern "C" int launch_fused_predict_linear_packed(
+    const uint64_t* packed, const float* diff, const float* base,
+    const float* wbg, const float* lfnull, float* ey, int B, int S, int Mpad,
+    int Npad, int n_out, int act, int link, hipStream_t stream)
+{
+    if (Mpad < 4 || Mpad > MAX_MPAD || Mpad % 4 != 0 || Npad % 16 != 0
+            || Npad < 16 || Npad / 16 > 8)
+        return -1;
+    if (link != 0 && (link != 1 || lfnull == nullptr)) return -1;
+    if (B <= 0 || S <= 0) return 0;
+    switch (n_out) {
+        case 1: return launch_fpp_act<1>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, act, link, stream);
+        case 2: return launch_fpp_act<2>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, act, link, stream);
+        case 4: return launch_fpp_act<4>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, act, link, stream);
+        default: return -1;
+    }
+}
+
+// K7p: wls_solve_mfma_kernel with the kernel weights read as the (S,) vector
+// every instance shares, and the result written straight into
+// phi_full (B, G, n_out): group vidx[k] receives phi[k], every other group of
+// the row receives 0.  Gram, Cholesky and solve arithmetic are unchanged.
+__global__ __launch_bounds__(256)
+void wls_solve_packed_kernel(
+    const uint64_t* __restrict__ packed, // (B, S)
+    const float* __restrict__ kw,        // (S,)
+    const float* __restrict__ ey_adj,    // (B, S, n_out)
+    const float* __restrict__ total,     // (B, n_out)
+    const int64_t* __restrict__ vidx,    // (M,)
+    float* __restrict__ phi_full,        // (B, G, n_out)
+    int B, int S, int M, int n_out, int G)
+{
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wv = tid >> 6;
+    const int mm = M - 1;
+    const int cols = mm + n_out;         // <= 16
+
+    __shared__ uint64_t pk[WLS_CHUNK];
+    __shared__ float wch[WLS_CHUNK];
+    __shared__ float eych[WLS_CHUNK][WLS_MAX_NOUT];
+    __shared__ float tileA[4][16][17];
+    __shared__ float A[16 * 16];
+    __shared__ float rhs[16 * WLS_MAX_NOUT];
+    __shared__ float tot_s[WLS_MAX_NOUT];
+    __shared__ float phi_s[17 * WLS_MAX_NOUT];
+    __shared__ int g_s[17];
+
+    if (tid < n_out) tot_s[tid] = total[(size_t)b * n_out + tid];
+    if (tid < M) g_s[tid] = (int)vidx[tid];
+    __syncthreads();
+
+    const uint64_t* pbase = packed + (size_t)b * S;
+    const float* eyb = ey_adj + (size_t)b * S * n_out;
+
+    const int arow = lane & 15;
+    const int akk = lane >> 4;
+
+    f32x4 acc = (f32x4){0, 0, 0, 0};
+
+    for (int c0 = 0; c0 < S; c0 += WLS_CHUNK) {
+        const int clen = min(WLS_CHUNK, S - c0);
+        // each wave stages exactly the samples it consumes (see
+        // wls_solve_mfma_kernel): no barrier, only an LDS wait
+        if (tid < clen) {
+            uint64_t bits = pbase[c0 + tid];
+            pk[tid] = bits;
+            wch[tid] = kw[c0 + tid];
+            float mlast = (float)((bits >> (M - 1)) & 1ull);
+            for (int o = 0; o < n_out; ++o)
+                eych[tid][o] = eyb[(size_t)(c0 + tid) * n_out + o] - mlast * tot_s[o];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        const int base = wv * 64;
+        for (int ks = 0; ks < 64; ks += 4) {
+            int t = base + ks + akk;
+            float a = 0.0f, bv = 0.0f;
+            if (t < clen) {
+                uint64_t bits = pk[t];
+                float ml = (float)((bits >> (M - 1)) & 1ull);
+                float w = wch[t];
+                if (arow < mm) a = (float)((bits >> arow) & 1ull) - ml;
+                if (arow < mm) bv = w * ((float)((bits >> arow) & 1ull) - ml);
+                else if (arow < cols) bv = w * eych[t][arow - mm];
+            }
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        tileA[wv][(lane >> 4) * 4 + r][lane & 15] = acc[r];
+    __syncthreads();
+    for (int idx = tid; idx < 16 * 16; idx += 256) {
+        int i = idx / 16, j = idx % 16;
+        float v = tileA[0][i][j] + tileA[1][i][j] + tileA[2][i][j] + tileA[3][i][j];
+        if (j < mm) A[i * mm + j] = v;
+        else if (j < cols && i < mm) rhs[i * n_out + (j - mm)] = v;
+    }
+    __syncthreads();
+
+    if (tid == 0) {
+        for (int k = 0; k < mm; ++k) {
+            float d = A[k * mm + k];
+            for (int t = 0; t < k; ++t) d -= A[k * mm + t] * A[k * mm + t];
+            d = sqrtf(fmaxf(d, 1e-20f));
+            A[k * mm + k] = d;
+            float inv = 1.0f / d;
+            for (int r = k + 1; r < mm; ++r) {
+                float v = A[r * mm + k];
+                for (int t = 0; t < k; ++t) v -= A[r * mm + t] * A[k * mm + t];
+                A[r * mm + k] = v * inv;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < n_out) {
+        const int o = tid;
+        float y[16];
+        for (int i = 0; i < mm; ++i) {
+            float v = rhs[i * n_out + o];
+            for (int t = 0; t < i; ++t) v -= A[i * mm + t] * y[t];
+            y[i] = v / A[i * mm + i];
+        }
+        float w[16];
+        float sumw = 0.0f;
+        for (int i = mm - 1; i >= 0; --i) {
+            float v = y[i];
+            for (int t = i + 1; t < mm; ++t) v -= A[t * mm + i] * w[t];
+            w[i] = v / A[i * mm + i];
+        }
+        for (int i = 0; i < mm; ++i) sumw += w[i];
+        for (int i = 0; i < mm; ++i) phi_s[i * n_out + o] = w[i];
+        phi_s[(M - 1) * n_out + o] = tot_s[o] - sumw;
+    }
+    __syncthreads();
+    // every element of the row is written exactly once
+    float* prow = phi_full + (size_t)b * G * n_out;
+    for (int idx = tid; idx < G * n_out; idx += 256) {
+        const int g = idx / n_out, o = idx % n_out;
+        float v = 0.0f;
+        for (int k = 0; k < M; ++k)
+            if (g_s[k] == g) v = phi_s[k * n_out + o];
+        prow[idx] = v;
+    }
+}
+
+extern "C" int launch_wls_solve_packed(
+    const uint64_t* packed, const float* kw, const float* ey_adj,
+    const float* total, const int64_t* vidx, float* phi_full, int B, int S,
+    int M, int n_out, int G, hipStream_t stream)
+{
+    if (M < 2 || M > G || n_out < 1 || n_out > WLS_MAX_NOUT
+            || (M - 1) + n_out > 16)
+        return -1;
+    if (B <= 0) return 0;
+    wls_solve_packed_kernel<<<dim3(B), dim3(256), 0, stream>>>(
+        packed, kw, ey_adj, total, vidx, phi_full, B, S, M, n_out, G);
+    return 0;
+}
