@@ -22,6 +22,13 @@ paths print a per-stage trace.
     # a forest shape (about 280 internal nodes per tree): the walk kernel;
     # the module path explains fewer rows so that it ends within --timeout
     python benchmarks/trees_fused.py --depth 12 --p-stop 0.2 --module-instances 8
+    # the same forest as a routed ensemble (RoutedTreeEnsemblePredictor):
+    # missing_left set with --p-missing-left (0.5), the splits on the last
+    # --n-categorical (8) features categorical, those columns holding
+    # category codes, NaN in --p-nan (5 %) of the entries of the instances
+    # and of the background
+    python benchmarks/trees_fused.py --routed --depth 12 --p-stop 0.2 \
+        --module-instances 8
 """
 from __future__ import annotations
 
@@ -45,6 +52,29 @@ PATHS = {
 }
 
 
+def routed_problem(args, kind, data):
+    """The forest of the unrouted run with routing added, and ``data``
+    changed in place: category codes in the last columns, NaN sprinkled over
+    the instances and the background."""
+    import numpy as np
+
+    from distributedkernelshap_amd.models import (RoutedTreeEnsemblePredictor,
+                                                  TorchPredictor)
+
+    pred = RoutedTreeEnsemblePredictor.random(
+        64, 2, seed=0, trees=args.trees, depth=args.depth, p_stop=args.p_stop,
+        p_missing_left=args.p_missing_left, n_categorical=args.n_categorical)
+    rng = np.random.Generator(np.random.Philox(key=[1000, 0x207ED]))
+    for a in (data.X, data.background):
+        if args.n_categorical:
+            a[:, -args.n_categorical:] = rng.integers(
+                0, 256, size=(a.shape[0], args.n_categorical))
+        a[rng.uniform(size=a.shape) < args.p_nan] = np.nan
+    if kind == "trees_fused":
+        return pred
+    return TorchPredictor(pred.build_module(), device="cuda")
+
+
 def run_path(args) -> dict:
     import numpy as np
     import torch
@@ -63,8 +93,11 @@ def run_path(args) -> dict:
         n_features=64, n_instances=args.instances,
         n_background=args.background, seed=1000,
     )
-    pred = make_predictor(kind, 64, 2, seed=0, trees=args.trees,
-                          depth=args.depth, p_stop=args.p_stop)
+    if args.routed:
+        pred = routed_problem(args, kind, data)
+    else:
+        pred = make_predictor(kind, 64, 2, seed=0, trees=args.trees,
+                              depth=args.depth, p_stop=args.p_stop)
     engine = KernelShapEngine(
         pred, data.background, groups=data.groups, link="logit", seed=0,
         device=device,
@@ -92,6 +125,7 @@ def run_path(args) -> dict:
         "instances": instances,
         "trees": args.trees,
         "depth": args.depth,
+        "routed": bool(args.routed),
         "steps": steps,
         "warmup": warmup,
         "expl_per_s_median": instances / med,
@@ -137,6 +171,17 @@ def main() -> None:
     ap.add_argument("--depth", type=int, default=4)
     ap.add_argument("--p-stop", type=float, default=0.2,
                     help="probability that a branch below the root ends early")
+    ap.add_argument("--routed", action="store_true",
+                    help="the same forest with missing-value and categorical "
+                         "routing, NaN in the rows (RoutedTreeEnsemblePredictor)")
+    ap.add_argument("--n-categorical", type=int, default=8,
+                    help="--routed: the last N of the 64 features hold "
+                         "category codes and split categorically")
+    ap.add_argument("--p-nan", type=float, default=0.05,
+                    help="--routed: share of NaN entries in the instances "
+                         "and in the background")
+    ap.add_argument("--p-missing-left", type=float, default=0.5,
+                    help="--routed: probability of a split's missing_left flag")
     ap.add_argument("--module-instances", type=int, default=None,
                     help="instances the module path explains (default: "
                          "--instances); for deep shapes")
@@ -166,6 +211,10 @@ def main() -> None:
     ]
     if args.module_instances is not None:
         passthrough += ["--module-instances", str(args.module_instances)]
+    if args.routed:
+        passthrough += ["--routed", "--n-categorical", str(args.n_categorical),
+                        "--p-nan", str(args.p_nan),
+                        "--p-missing-left", str(args.p_missing_left)]
     for name in ("module", "fused", "cpu"):
         cmd = [sys.executable, os.path.abspath(__file__), "--path", name]
         try:

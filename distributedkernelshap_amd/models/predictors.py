@@ -15,6 +15,9 @@ Here predictors are first-class objects:
   forests) with explicit node tables; exposes ``tree_params()`` so the GPU
   engine can run the fused tree HIP kernel (split decisions packed to bits
   once per row, a bitwise select and a bit-register walk per sample).
+* ``RoutedTreeEnsemblePredictor`` — the same with per-node routing of
+  missing values and categorical (bitset) splits: ``HistGradientBoosting*``
+  and forests fitted on data with NaN.
 * ``KernelMachinePredictor`` — kernel SVM / kernel ridge (rbf or polynomial
   kernel) with explicit support vectors and dual coefficients; exposes
   ``kernel_machine_params()`` so the GPU engine can run the fused
@@ -32,7 +35,8 @@ from typing import Optional
 import numpy as np
 
 __all__ = ["KernelMachinePredictor", "LinearPredictor", "MLPPredictor",
-           "TorchPredictor", "TreeEnsemblePredictor", "make_predictor"]
+           "RoutedTreeEnsemblePredictor", "TorchPredictor",
+           "TreeEnsemblePredictor", "make_predictor"]
 
 
 def _softmax(z: np.ndarray) -> np.ndarray:
@@ -294,9 +298,13 @@ class TreeEnsemblePredictor:
     NaN inputs are not supported: sklearn >= 1.3 routes a missing value per
     node (``missing_go_to_left``), which these tables do not carry.
     ``__call__`` raises ``ValueError`` on a NaN; the GPU paths do not look.
+    ``RoutedTreeEnsemblePredictor`` carries per-node missing-value routing
+    and categorical splits (``HistGradientBoosting*``, forests fitted on
+    data with NaN).
     """
 
     _OUT = ("softmax", "sigmoid", "none")
+    _INF_THRESHOLD = False      # +inf thresholds (routed ensembles only)
 
     def __init__(self, trees, n_features: int, n_out: int, base=None,
                  scale: float = 1.0, out_col=None, activation: str = "none"):
@@ -343,8 +351,12 @@ class TreeEnsemblePredictor:
                     f"tree {ti}: children must form one tree rooted at node 0")
             if np.any(feat[internal] < 0) or np.any(feat[internal] >= n_features):
                 raise ValueError(f"tree {ti}: split feature out of range")
-            if not np.all(np.isfinite(thr[internal])):
-                raise ValueError(f"tree {ti}: thresholds must be finite")
+            finite = np.isfinite(thr[internal])
+            if self._INF_THRESHOLD:
+                finite |= thr[internal] == np.inf
+            if not np.all(finite):
+                raise ValueError(f"tree {ti}: thresholds must be finite"
+                                 + (" or +inf" if self._INF_THRESHOLD else ""))
             self.trees.append({
                 "feature": np.where(internal, feat, 0), "threshold": thr,
                 "left": left, "right": right, "value": val,
@@ -529,7 +541,8 @@ class TreeEnsemblePredictor:
         if name.startswith("HistGradientBoosting"):
             raise TypeError(
                 f"{name} is not supported: it compares in float64 on binned "
-                "data and routes missing values and categories separately")
+                "data and routes missing values and categories separately "
+                "(use RoutedTreeEnsemblePredictor.from_sklearn)")
         from sklearn.ensemble import (ExtraTreesClassifier, ExtraTreesRegressor,
                                       GradientBoostingClassifier,
                                       GradientBoostingRegressor,
@@ -604,6 +617,334 @@ class TreeEnsemblePredictor:
             f"{name} is not a supported tree model (DecisionTree*, "
             "RandomForest*, ExtraTrees*, GradientBoostingRegressor, "
             "GradientBoostingClassifier with log_loss)")
+
+
+class RoutedTreeEnsemblePredictor(TreeEnsemblePredictor):
+    """``TreeEnsemblePredictor`` with per-node routing of missing values and
+    categorical splits (sklearn's ``HistGradientBoosting*``, and trees and
+    forests fitted on data with NaN).
+
+    Each tree dict may carry, next to the parent's arrays, ``missing_left``
+    ``(n_nodes,)`` bool and ``cat_row`` ``(n_nodes,)`` int: -1 marks a numeric
+    split, any other value a row of ``cat_left`` ``(C, 8)`` uint32, a bitset
+    of 256 bits in which bit c set means "category code c goes left".
+    ``categories`` optionally maps a feature to the sorted array of its known
+    raw category values.
+
+    Encoding, once per row (``encode``): a feature listed in ``categories``
+    is replaced by the index of its float32-rounded value in that array, or
+    NaN when the value is absent or NaN; every other feature is rounded to
+    float32. Known category values must be exactly representable in float32,
+    so that the lookup on float32 device rows agrees.
+
+    At a node, for the encoded value v:
+
+    * numeric: NaN routes by ``missing_left``; otherwise ``float64(v) <=
+      threshold`` goes left. The threshold is finite or ``+inf`` ("every
+      non-missing value goes left").
+    * categorical: NaN, ``v < 0`` and ``v >= 256`` route by ``missing_left``;
+      otherwise ``c = trunc(v)`` goes left iff bit c of the node's bitset is
+      set. sklearn casts the value to ``uint8`` without a range check, which
+      is undefined for ``v >= 256``; routing it as missing is this class's
+      defined behaviour.
+
+    sklearn's three-way rule (left set / known set / unknown treated as
+    missing) is folded into the bitset at import:
+    ``cat_left = raw_left | (missing_left ? ~known : 0)``.
+
+    ``__call__`` is the numpy oracle with exactly this rule; NaN is a legal
+    input. ``tree_params()`` adds a ``"routing"`` entry, which makes the GPU
+    engine use the routed forms of both fused kernels.
+    """
+
+    _INF_THRESHOLD = True
+    CAT_CODES = 256
+
+    def __init__(self, trees, n_features: int, n_out: int, base=None,
+                 scale: float = 1.0, out_col=None, activation: str = "none",
+                 cat_left=None, categories=None):
+        super().__init__(trees, n_features, n_out, base=base, scale=scale,
+                         out_col=out_col, activation=activation)
+        cl = (np.zeros((0, 8), dtype=np.uint32) if cat_left is None
+              else np.asarray(cat_left))
+        if cl.ndim != 2 or cl.shape[1] != 8 or cl.dtype != np.uint32:
+            raise ValueError(
+                "cat_left must be a (C, 8) uint32 array: 256 bits per "
+                "categorical node")
+        self.cat_left = cl.copy()
+        for ti, (tr, own) in enumerate(zip(trees, self.trees)):
+            nn_ = own["left"].shape[0]
+            internal = own["left"] >= 0
+            ml = np.asarray(tr.get("missing_left", np.zeros(nn_, dtype=bool)))
+            cr = np.asarray(tr.get("cat_row", np.full(nn_, -1)))
+            ml, cr = ml.reshape(-1), cr.reshape(-1).astype(np.int64)
+            if ml.shape[0] != nn_ or cr.shape[0] != nn_:
+                raise ValueError(
+                    f"tree {ti}: missing_left and cat_row must have one "
+                    "entry per node")
+            cr = np.where(internal, cr, -1)
+            if np.any(cr < -1) or np.any(cr >= cl.shape[0]):
+                raise ValueError(
+                    f"tree {ti}: cat_row must be -1 or a row of cat_left "
+                    f"({cl.shape[0]} rows)")
+            own["missing_left"] = ml.astype(bool) & internal
+            own["cat_row"] = cr
+            # a categorical split has no threshold
+            own["threshold"] = np.where(cr >= 0, 0.0, own["threshold"])
+        self.categories = {}
+        for f, c in sorted((categories or {}).items()):
+            f = int(f)
+            c = np.asarray(c, dtype=np.float64).reshape(-1)
+            if not 0 <= f < n_features:
+                raise ValueError(f"categories: feature {f} out of range")
+            if c.size < 1 or not np.all(np.isfinite(c)) \
+                    or np.any(np.diff(c) <= 0):
+                raise ValueError(
+                    f"categories[{f}] must be finite, sorted and distinct")
+            with np.errstate(over="ignore"):
+                exact = c.astype(np.float32).astype(np.float64) == c
+            if not np.all(exact):
+                raise ValueError(
+                    f"categories[{f}] must be exactly representable in "
+                    "float32")
+            self.categories[f] = c
+
+    # ------------------------------------------------------------------ #
+
+    def encode(self, X: np.ndarray) -> np.ndarray:
+        """Rows as the nodes see them (fp64 holding float32 values): features
+        in ``categories`` replaced by their category index or NaN, the others
+        rounded to float32."""
+        X = np.asarray(X)
+        if X.ndim != 2 or X.shape[1] != self.n_features:
+            raise ValueError(f"X must be (n, {self.n_features})")
+        with np.errstate(over="ignore"):
+            enc = X.astype(np.float32).astype(np.float64)
+        for f, c in self.categories.items():
+            v = enc[:, f]
+            k = np.minimum(np.searchsorted(c, v), c.shape[0] - 1)
+            enc[:, f] = np.where(c[k] == v, k.astype(np.float64), np.nan)
+        return enc
+
+    def _flatten(self):
+        if self._flat is None:
+            f = super()._flatten()
+            f["missing_left"] = np.concatenate(
+                [tr["missing_left"] for tr in self.trees])
+            f["cat_row"] = np.concatenate([tr["cat_row"] for tr in self.trees])
+            f["cat_left"] = self.cat_left
+            f["categories"] = self.categories
+        return self._flat
+
+    def _go_left(self, f, v, idx):
+        """The routing rule for encoded values ``v`` at flat nodes ``idx``."""
+        ml = f["missing_left"][idx]
+        cr = f["cat_row"][idx]
+        nan = np.isnan(v)
+        with np.errstate(invalid="ignore"):
+            num = np.where(nan, ml, v <= f["threshold"][idx])
+            if f["cat_left"].shape[0] == 0:
+                return num
+            missing = nan | (v < 0) | (v >= self.CAT_CODES)
+        c = np.where(missing, 0.0, v).astype(np.int64)          # truncates
+        word = f["cat_left"][np.maximum(cr, 0), c >> 5]
+        bit = ((word >> (c & 31).astype(np.uint32)) & np.uint32(1)) != 0
+        return np.where(cr >= 0, np.where(missing, ml, bit), num)
+
+    def raw(self, X: np.ndarray) -> np.ndarray:
+        """``base + scale · Σ_t leaf`` before the activation (fp64)."""
+        f = self._flatten()
+        enc = self.encode(X)
+        out = np.empty((enc.shape[0], self._n_out))
+        step = max(1, (1 << 22) // self.n_trees)
+        for lo in range(0, enc.shape[0], step):
+            xs = enc[lo : lo + step]
+            rows = np.arange(xs.shape[0])[:, None]
+            idx = np.broadcast_to(f["roots"][None, :], (xs.shape[0], self.n_trees))
+            for _ in range(f["depth"]):
+                go_left = self._go_left(f, xs[rows, f["feature"][idx]], idx)
+                idx = np.where(go_left, f["left"][idx], f["right"][idx])
+            out[lo : lo + step] = self.base + self.scale * f["value"][idx].sum(axis=1)
+        return out
+
+    def tree_params(self):
+        params = super().tree_params()
+        params["routing"] = {"cat_left": self.cat_left,
+                             "categories": self.categories}
+        return params
+
+    # ------------------------------------------------------------------ #
+
+    @classmethod
+    def random(cls, d: int, n_out: int = 2, trees: int = 100, depth: int = 4,
+               seed: int = 0, activation: str = "softmax",
+               vector_leaves: bool = False, p_stop: float = 0.2,
+               p_missing_left: float = 0.5, n_categorical: int = 0):
+        """The forest ``TreeEnsemblePredictor.random`` draws for the same
+        arguments, with ``missing_left`` set with probability
+        ``p_missing_left`` per split and every split on one of the last
+        ``n_categorical`` features turned into a categorical split with a
+        random 256-bit set (those features then hold category codes)."""
+        plain = TreeEnsemblePredictor.random(
+            d, n_out, trees=trees, depth=depth, seed=seed,
+            activation=activation, vector_leaves=vector_leaves, p_stop=p_stop)
+        rng = np.random.Generator(np.random.Philox(key=[seed, 0x207ED]))
+        out, sets = [], []
+        for tr in plain.trees:
+            nn_ = tr["left"].shape[0]
+            cat = (tr["left"] >= 0) & (tr["feature"] >= d - n_categorical)
+            cr = np.full(nn_, -1, dtype=np.int64)
+            cr[cat] = len(sets) + np.arange(int(cat.sum()))
+            for _ in range(int(cat.sum())):
+                sets.append(rng.integers(0, 2**32, size=8, dtype=np.uint64)
+                            .astype(np.uint32))
+            out.append(dict(tr, missing_left=rng.uniform(size=nn_) < p_missing_left,
+                            cat_row=cr))
+        cat_left = (np.stack(sets) if sets else None)
+        return cls(out, d, n_out, base=plain.base, scale=plain.scale,
+                   out_col=plain.out_col, activation=activation,
+                   cat_left=cat_left)
+
+    @classmethod
+    def from_sklearn(cls, est):
+        """Wrap a fitted ``HistGradientBoostingClassifier`` (binary or
+        multiclass), a ``HistGradientBoostingRegressor`` with an identity
+        link (``squared_error``, ``absolute_error``, ``quantile``), or a
+        ``DecisionTree*`` / ``RandomForest*`` / ``ExtraTrees*`` model, whose
+        ``tree_.missing_go_to_left`` is carried. Raises ``TypeError`` with
+        the reason for anything else."""
+        name = type(est).__name__
+        if not type(est).__module__.startswith("sklearn."):
+            raise TypeError(f"{name} is not a sklearn estimator")
+        if name in ("HistGradientBoostingClassifier",
+                    "HistGradientBoostingRegressor"):
+            return cls._from_hist_gradient_boosting(est)
+        from sklearn.ensemble import (ExtraTreesClassifier, ExtraTreesRegressor,
+                                      RandomForestClassifier,
+                                      RandomForestRegressor)
+        from sklearn.tree import DecisionTreeClassifier, DecisionTreeRegressor
+
+        classes = isinstance(est, (DecisionTreeClassifier, RandomForestClassifier,
+                                   ExtraTreesClassifier))
+        if not classes and not isinstance(
+                est, (DecisionTreeRegressor, RandomForestRegressor,
+                      ExtraTreesRegressor)):
+            raise TypeError(
+                f"{name} has no missing-value or categorical routing to "
+                "carry (supported here: HistGradientBoosting*, DecisionTree*, "
+                "RandomForest*, ExtraTrees*); try "
+                "TreeEnsemblePredictor.from_sklearn")
+        if getattr(est, "n_outputs_", 1) != 1:
+            raise TypeError(
+                f"{name} was fitted on {est.n_outputs_} outputs; multi-output "
+                "estimators are not supported")
+        members = list(getattr(est, "estimators_", [est]))
+        tables = []
+        for m in members:
+            t = m.tree_
+            v = t.value[:, 0, :]
+            v = v / v.sum(axis=1, keepdims=True) if classes else v[:, 0]
+            if not hasattr(t, "missing_go_to_left"):
+                raise TypeError(
+                    f"{name}: tree_.missing_go_to_left is missing (sklearn "
+                    ">= 1.3 is needed)")
+            tables.append({"feature": t.feature, "threshold": t.threshold,
+                           "left": t.children_left, "right": t.children_right,
+                           "value": v,
+                           "missing_left": t.missing_go_to_left != 0})
+        return cls(tables, int(est.n_features_in_),
+                   len(est.classes_) if classes else 1,
+                   scale=1.0 / len(members), activation="none")
+
+    @classmethod
+    def _from_hist_gradient_boosting(cls, est):
+        name = type(est).__name__
+        classifier = name.endswith("Classifier")
+        if not classifier and est.loss not in ("squared_error", "absolute_error",
+                                               "quantile"):
+            raise TypeError(
+                f"{name}(loss={est.loss!r}) is not supported: only identity-"
+                "link losses (squared_error, absolute_error, quantile)")
+        try:
+            stages = est._predictors
+            mapper = est._bin_mapper
+            pre = est._preprocessor
+            known, f_idx_map = mapper.make_known_categories_bitsets()
+            d = int(est.n_features_in_)
+            # column j of what the trees saw is column orig[j] of the caller
+            orig = np.arange(d)
+            categories = {}
+            if pre is not None:
+                is_cat = np.asarray(est.is_categorical_, dtype=bool)
+                orig = np.concatenate([np.flatnonzero(is_cat),
+                                       np.flatnonzero(~is_cat)])
+                enc = pre.named_transformers_["encoder"]
+                for f, c in zip(np.flatnonzero(is_cat), enc.categories_):
+                    c = np.asarray(c, dtype=np.float64)
+                    categories[int(f)] = c[~np.isnan(c)]
+            trees, sets, cols = [], [], []
+            for stage in stages:
+                for k, tp in enumerate(stage):
+                    nd = tp.nodes
+                    leaf = nd["is_leaf"] != 0
+                    cat = (nd["is_categorical"] != 0) & ~leaf
+                    ml = (nd["missing_go_to_left"] != 0) & ~leaf
+                    fidx = np.where(leaf, 0, nd["feature_idx"]).astype(np.int64)
+                    cr = np.full(nd.shape[0], -1, dtype=np.int64)
+                    for i in np.flatnonzero(cat):
+                        bits = np.asarray(
+                            tp.raw_left_cat_bitsets[nd["bitset_idx"][i]],
+                            dtype=np.uint32).copy()
+                        if ml[i]:
+                            # unknown categories are missing values
+                            bits |= ~np.asarray(known[f_idx_map[fidx[i]]],
+                                                dtype=np.uint32)
+                        cr[i] = len(sets)
+                        sets.append(bits)
+                    trees.append({
+                        "feature": orig[fidx],
+                        "threshold": np.where(leaf | cat, 0.0, nd["num_threshold"]),
+                        "left": np.where(leaf, -1, nd["left"].astype(np.int64)),
+                        "right": np.where(leaf, -1, nd["right"].astype(np.int64)),
+                        "value": nd["value"].astype(np.float64),
+                        "missing_left": ml, "cat_row": cr,
+                    })
+                    cols.append(k)
+            k = len(stages[0])
+        except (AttributeError, KeyError, IndexError, ValueError) as exc:
+            raise TypeError(
+                f"{name}: a private attribute this import reads is missing or "
+                f"different in this sklearn version ({exc})") from exc
+        if classifier:
+            n_out = len(est.classes_)
+            if k == 1:
+                cols = [1] * len(trees)
+            act, score = "softmax", est.decision_function
+        else:
+            n_out, act, score = 1, "none", est.predict
+        try:
+            pred = cls(trees, d, n_out, scale=1.0, out_col=cols, activation=act,
+                       cat_left=np.stack(sets) if sets else None,
+                       categories=categories)
+        except ValueError as exc:
+            raise TypeError(f"{name}: {exc}") from exc
+        # the constant baseline, from the public API only: the score minus
+        # our own tree sum, which must not depend on the row
+        rng = np.random.Generator(np.random.Philox(key=[0, 0xBA5E]))
+        probes = np.vstack([np.zeros(d), 10.0 * rng.normal(size=(2, d))])
+        probes = probes.astype(np.float32).astype(np.float64)
+        sc = np.asarray(score(probes), dtype=np.float64).reshape(3, -1)
+        own = pred.raw(probes)
+        resid = sc - (own[:, 1:2] if (k == 1 and n_out == 2) else own)
+        if np.abs(resid - resid[0]).max() > 1e-9 * (1.0 + np.abs(sc).max()):
+            raise TypeError(
+                f"{name}: the score minus the tree sum is not constant; the "
+                "routing rule of this sklearn version differs")
+        if k == 1 and n_out == 2:
+            pred.base = np.array([0.0, float(resid[0, 0])])
+        else:
+            pred.base = resid[0].copy()
+        return pred
 
 
 class KernelMachinePredictor:

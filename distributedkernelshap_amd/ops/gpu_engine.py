@@ -353,7 +353,11 @@ class GpuKernelShap:
 
     # ------------------------------------------------------------------ #
     # TreeEnsemblePredictor: fused_predict_trees (K4t) with the gather
-    # traversal torch module as the out-of-envelope fallback
+    # traversal torch module as the out-of-envelope fallback.  A routed
+    # ensemble (tree_params() carries "routing": missing values and
+    # categorical splits) takes the same three paths: the modules and
+    # decision_bits encode raw rows themselves, the walk kernel reads rows
+    # encoded once (the background at fit, the instances per call)
 
     def _init_trees(self, predictor):
         from . import tree_pack
@@ -412,6 +416,9 @@ class GpuKernelShap:
         if walk:
             self.trees["pack"] = tree_pack.pack_trees_walk(
                 params, self.engine._col_group, self.device)
+            # routed tables: the background as the nodes see it
+            self.trees["bg_enc"] = tree_pack.encode_rows(
+                self.trees["pack"], self.bg)
             self.trees_fused = True
             self.trees_kernel = "walk"
             return
@@ -437,10 +444,12 @@ class GpuKernelShap:
         vmap = t.tensor(vmap_h, device=self.device)
         ey = self._buf("ey", (b, s, self.n_out))
         if self.trees_kernel == "walk":
-            # K4w reads the float32 rows themselves: no decision bits
+            # K4w reads the float32 rows themselves (encoded, for routed
+            # tables): no decision bits
             return tree_pack.fused_predict_walk(
                 self.ext, pack, masks.contiguous(), vmap,
-                X_dev.float().contiguous(), self.bg, self.bg_w, ey,
+                tree_pack.encode_rows(pack, X_dev), self.trees["bg_enc"],
+                self.bg_w, ey,
             )
         dx = tree_pack.decision_bits(pack, X_dev)
         return tree_pack.fused_predict(

@@ -115,7 +115,8 @@ extern "C" int launch_fused_predict_trees_walk(
     const int* nodes, const int* roots, const float* leaves, const float* base,
     const float* wbg, float* ey, float scale,
     int B, int S, int Mv, int N, int D, int G, int T, int R, int L,
-    int max_depth, int n_out, int act, int leaf_mode, hipStream_t stream);
+    int max_depth, int n_out, int act, int leaf_mode,
+    const unsigned* cat_left, int C, hipStream_t stream);
 
 // km_kernels.hip
 extern "C" int launch_fused_predict_kernelmachine(
@@ -633,7 +634,8 @@ void fused_predict_trees_walk(
     torch::Tensor masks, torch::Tensor vmap, torch::Tensor x, torch::Tensor bg,
     torch::Tensor nodes, torch::Tensor roots, torch::Tensor leaves,
     torch::Tensor base, double scale, torch::Tensor wbg, torch::Tensor ey,
-    int64_t act, int64_t leaf_mode, int64_t max_depth) {
+    int64_t act, int64_t leaf_mode, int64_t max_depth,
+    c10::optional<torch::Tensor> cat_left) {
     static const char* envelope =
         "fused_predict_trees_walk: outside the supported envelope (depth <= "
         "64, n_out <= 8, at most 1024 groups and 4096 features, node records "
@@ -670,6 +672,19 @@ void fused_predict_trees_walk(
     TORCH_CHECK(wbg.dtype() == torch::kFloat32 && wbg.numel() == N,
                 "wbg must be f32 (N)");
     TORCH_CHECK(max_depth >= 0 && max_depth <= 64, envelope);
+    // routed tables: x and bg are encoded rows, cat_left the bitset rows
+    const unsigned* cat_ptr = nullptr;
+    int64_t C = 0;
+    if (cat_left.has_value()) {
+        const torch::Tensor& cl = *cat_left;
+        CHECK_DEV(cl);
+        TORCH_CHECK(cl.dtype() == torch::kInt32 && cl.dim() == 2
+                    && cl.size(1) == 8 && cl.size(0) >= 1,
+                    "cat_left must be int32 (C,8) with C >= 1");
+        TORCH_CHECK(cl.size(0) <= 0x7fffffffLL / 8, envelope);
+        cat_ptr = reinterpret_cast<const unsigned*>(cl.data_ptr<int>());
+        C = cl.size(0);
+    }
     TORCH_CHECK(nodes.size(0) <= 0x7fffffffLL && leaves.size(0) <= 0x7fffffffLL
                 && roots.size(0) <= 0x7fffffffLL && D <= 0x7fffffffLL
                 && vmap.size(0) <= 0x7fffffffLL, envelope);
@@ -680,7 +695,7 @@ void fused_predict_trees_walk(
         ey.data_ptr<float>(), (float)scale, B, S, Mv, N, (int)D,
         (int)vmap.size(0), (int)roots.size(0), (int)nodes.size(0),
         (int)leaves.size(0), (int)max_depth, n_out, (int)act, (int)leaf_mode,
-        current_stream());
+        cat_ptr, (int)C, current_stream());
     TORCH_CHECK(rc != -2, "fused_predict_trees_walk: LDS size attribute rejected");
     TORCH_CHECK(rc == 0, envelope);
 }
@@ -760,7 +775,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("leaves"), pybind11::arg("base"),
           pybind11::arg("scale"), pybind11::arg("wbg"), pybind11::arg("ey"),
           pybind11::arg("act"), pybind11::arg("leaf_mode"),
-          pybind11::arg("max_depth"));
+          pybind11::arg("max_depth"),
+          pybind11::arg("cat_left") = pybind11::none());
     m.def("fused_predict_mlp", &fused_predict_mlp,
           "fused MLP predict (K4m): first layer folded over varying groups, "
           "hidden activations in LDS, f32 or bf16 MFMA by operand dtype",

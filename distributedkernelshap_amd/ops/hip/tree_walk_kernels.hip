@@ -35,9 +35,25 @@
 // record loads overlap (measured: 1.48x one tree at a time; four gain 1.5 %
 // more).
 //
-// Every index taken from a record is clamped before it is used, and a walk
-// ends after 64 steps: a malformed table gives wrong numbers, never a read
-// out of bounds or a spin.
+// Routed tables (ROUTED = true; RoutedTreeEnsemblePredictor): x and bg hold
+// encoded rows (a feature with known categories is its category index or
+// NaN) and a split record carries two flags above the group in [2]:
+//     bit 30  a missing value goes left
+//     bit 29  categorical split; [0] is then a row of cat_left (C, 8) u32,
+//             a bitset of 256 bits, bit c set = "code c goes left"
+// The step becomes
+//     numeric      left = (v != v) ? missing_left : v <= thr32
+//     categorical  missing = !(0 <= v < 256)          (true for NaN)
+//                  c = (int)v
+//                  left = missing ? missing_left
+//                                 : bit c of cat_left[row * 8 + (c >> 5)]
+// with one dependent dword load for a categorical split only.  The ROUTED =
+// false instantiations are the code they were before the flag existed.
+//
+// Every index taken from a record is clamped before it is used (the bitset
+// row to C - 1; the launcher refuses C < 1), and a walk ends after 64 steps:
+// a malformed table gives wrong numbers, never a read out of bounds or a
+// spin.
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -51,6 +67,10 @@
 #define TW_MAX_FEATURES 4096     // x row of 16 KiB in LDS
 #define TW_LDS_HALF (80 * 1024)  // two workgroups per CU
 #define TW_IL 2                  // trees walked per lane at a time
+#define TW_GROUP_MASK 0xffff     // routed record [2]: group in the low bits,
+#define TW_FLAG_MISSING_LEFT (1 << 30)   // then the two routing flags
+#define TW_FLAG_CATEGORICAL (1 << 29)
+#define TW_CAT_WORDS 8           // 256 bits per categorical split
 
 struct WalkArgs {
     const uint8_t* masks;        // (B, S, Mv) u8
@@ -67,9 +87,11 @@ struct WalkArgs {
     int B, S, Mv, N, D, G, T, R, L, n_out, act, leaf_mode;
     int gwords;                  // ceil(G / 64)
     unsigned x_bytes, gb_bytes;
+    const unsigned* cat_left;    // (C, 8) u32 bitsets, routed tables only
+    int C;
 };
 
-template <int NO, bool WIDE, bool BGL>
+template <int NO, bool WIDE, bool BGL, bool ROUTED>
 __global__ __launch_bounds__(TW_THREADS)
 void fused_predict_trees_walk_kernel(const WalkArgs p)
 {
@@ -112,6 +134,7 @@ void fused_predict_trees_walk_kernel(const WalkArgs p)
     // ---- main loop: lane = sample, wave = n slot --------------------------
     const uint64_t gb0 = gbL[lane];
     const unsigned rmax = (unsigned)p.R - 1u;
+    const unsigned cmax = ROUTED ? (unsigned)p.C - 1u : 0u;
     const int lstride = p.leaf_mode ? p.n_out : 1;
 
     float acc[NO];
@@ -144,15 +167,36 @@ void fused_predict_trees_walk_kernel(const WalkArgs p)
                 for (int k = 0; k < IL; ++k) {
                     if (rec[k].y >= 0) {
                         const int f = min(rec[k].y, D - 1);
-                        const int g = rec[k].z;
+                        const int g = ROUTED ? (rec[k].z & TW_GROUP_MASK)
+                                             : rec[k].z;
                         const uint64_t word = WIDE
                             ? gbL[min((int)((unsigned)g >> 6), p.gwords - 1) * 64 + lane]
                             : gb0;
                         const float vx = xL[f];
                         const float vb = bgrow[f];
                         const float v = ((word >> (g & 63)) & 1ull) ? vx : vb;
-                        const unsigned nx = v <= __int_as_float(rec[k].x)
-                            ? node[k] + 1u : (unsigned)rec[k].w;
+                        // a NaN compare is false and must not decide: the
+                        // explicit test sends a missing value by its flag.
+                        // Bitwise, not short-circuit: the numeric step stays
+                        // straight-line code (the loop is bound by the
+                        // instructions it issues, see docs/DESIGN.md)
+                        bool left = v <= __int_as_float(rec[k].x);
+                        if (ROUTED) {
+                            const bool ml = (rec[k].z & TW_FLAG_MISSING_LEFT) != 0;
+                            left = left | ((v != v) & ml);
+                            if (rec[k].z & TW_FLAG_CATEGORICAL) {
+                                // NaN fails both compares: the range test
+                                // comes before the float -> int conversion
+                                const bool known = v >= 0.0f && v < 256.0f;
+                                const int c = known ? (int)v : 0;
+                                const unsigned row = min((unsigned)rec[k].x, cmax);
+                                const unsigned w =
+                                    p.cat_left[row * TW_CAT_WORDS + (c >> 5)];
+                                left = known ? ((w >> (c & 31)) & 1u) != 0 : ml;
+                            }
+                        }
+                        const unsigned nx = left ? node[k] + 1u
+                                                 : (unsigned)rec[k].w;
                         node[k] = min(nx, rmax);
                         rec[k] = p.nodes[node[k]];
                     }
@@ -226,7 +270,7 @@ void fused_predict_trees_walk_kernel(const WalkArgs p)
 
 static size_t tw_round16(size_t v) { return (v + 15) / 16 * 16; }
 
-template <int NO, bool WIDE, bool BGL>
+template <int NO, bool WIDE, bool BGL, bool ROUTED>
 static int launch_walk_t(WalkArgs& a, size_t lds, hipStream_t stream)
 {
     if (lds > 48 * 1024) {
@@ -241,7 +285,7 @@ static int launch_walk_t(WalkArgs& a, size_t lds, hipStream_t stream)
         if (!cached || granted[dev] < lds) {
             if (hipFuncSetAttribute(
                     reinterpret_cast<const void*>(
-                        &fused_predict_trees_walk_kernel<NO, WIDE, BGL>),
+                        &fused_predict_trees_walk_kernel<NO, WIDE, BGL, ROUTED>),
                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
                 != hipSuccess)
                 return -2;
@@ -252,19 +296,28 @@ static int launch_walk_t(WalkArgs& a, size_t lds, hipStream_t stream)
     const long long nblk = (long long)a.B * n_tiles;
     if (nblk > 0x7fffffffLL) return -1;
     dim3 grid((unsigned)nblk), block(TW_THREADS);
-    fused_predict_trees_walk_kernel<NO, WIDE, BGL><<<grid, block, lds, stream>>>(a);
+    fused_predict_trees_walk_kernel<NO, WIDE, BGL, ROUTED>
+        <<<grid, block, lds, stream>>>(a);
     return 0;
+}
+
+template <int NO, bool ROUTED>
+static int launch_walk_r(WalkArgs& a, bool wide, bool bgl, size_t lds,
+                         hipStream_t stream)
+{
+    if (wide)
+        return bgl ? launch_walk_t<NO, true, true, ROUTED>(a, lds, stream)
+                   : launch_walk_t<NO, true, false, ROUTED>(a, lds, stream);
+    return bgl ? launch_walk_t<NO, false, true, ROUTED>(a, lds, stream)
+               : launch_walk_t<NO, false, false, ROUTED>(a, lds, stream);
 }
 
 template <int NO>
 static int launch_walk_no(WalkArgs& a, bool wide, bool bgl, size_t lds,
                           hipStream_t stream)
 {
-    if (wide)
-        return bgl ? launch_walk_t<NO, true, true>(a, lds, stream)
-                   : launch_walk_t<NO, true, false>(a, lds, stream);
-    return bgl ? launch_walk_t<NO, false, true>(a, lds, stream)
-               : launch_walk_t<NO, false, false>(a, lds, stream);
+    return a.cat_left ? launch_walk_r<NO, true>(a, wide, bgl, lds, stream)
+                      : launch_walk_r<NO, false>(a, wide, bgl, lds, stream);
 }
 
 // Returns -1 outside the supported envelope: any number of trees and records
@@ -273,13 +326,17 @@ static int launch_walk_no(WalkArgs& a, bool wide, bool bgl, size_t lds,
 // workgroup: 4 B x D (x row) + 512 B x ceil(G / 64) (group bitsets) + 4 B x
 // N x D (background, only while the three stay within 80 KiB), at least the
 // reduction scratch of 4 KiB x n_out rounded up to 1, 2, 4 or 8.
+// cat_left = nullptr (with C = 0) walks plain tables; a routed table passes
+// its C >= 1 bitset rows, and x and bg hold encoded rows.
 extern "C" int launch_fused_predict_trees_walk(
     const uint8_t* masks, const int* vmap, const float* x, const float* bg,
     const int* nodes, const int* roots, const float* leaves, const float* base,
     const float* wbg, float* ey, float scale,
     int B, int S, int Mv, int N, int D, int G, int T, int R, int L,
-    int max_depth, int n_out, int act, int leaf_mode, hipStream_t stream)
+    int max_depth, int n_out, int act, int leaf_mode,
+    const unsigned* cat_left, int C, hipStream_t stream)
 {
+    if (cat_left ? (C < 1 || C > 0x7fffffff / TW_CAT_WORDS) : C != 0) return -1;
     if (B < 1 || S < 1 || N < 1 || Mv < 1 || L < 1 || T < 1 || R < 1) return -1;
     if (D < 1 || D > TW_MAX_FEATURES) return -1;
     if (G < 1 || G > TW_MAX_GROUPS) return -1;
@@ -305,6 +362,7 @@ extern "C" int launch_fused_predict_trees_walk(
     a.L = L; a.n_out = n_out; a.act = act; a.leaf_mode = leaf_mode;
     a.gwords = gwords;
     a.x_bytes = (unsigned)x_bytes; a.gb_bytes = (unsigned)gb_bytes;
+    a.cat_left = cat_left; a.C = C;
 
     const bool wide = gwords > 1;
     switch (no) {

@@ -54,6 +54,34 @@ use a second, independent set of tables built by ``pack_trees_walk``:
   leaves      (L,) or (L, n_out) f32  leaf values, trees in order, a tree's
                                       leaves in preorder (the kernel reads
                                       the vector form only)
+
+Routed ensembles (``RoutedTreeEnsemblePredictor``: ``params`` carries a
+``"routing"`` entry) add to both sets of tables:
+
+  missing_left (T, Ipad) bool         bit-register pack only: a missing value
+                                      goes left at node i (pad slots: False)
+  cat_row     (T, Ipad) int64         bit-register pack only: -1 for a
+                                      numeric split, else a row of cat_left
+  cat_left    (max(C, 1), 8)          256 bits per categorical split, bit c
+                                      set = "category code c goes left";
+                                      int64 holding u32 words in the
+                                      bit-register pack (torch), int32 bit
+                                      patterns in the walk pack (kernel)
+  categories  {feature: f32 tensor}   sorted known category values of the
+                                      features that ``encode_rows`` replaces
+                                      by their category index (NaN when
+                                      absent)
+
+and the walk record of a split changes to
+
+  [0] the float32 threshold bits, or the cat_left row of a categorical split
+  [2] the coalition group in the low 16 bits, ``WALK_FLAG_MISSING_LEFT`` and
+      ``WALK_FLAG_CATEGORICAL`` above them (groups are <= 1,024)
+
+The rule at a node, for the encoded float32 value v: a numeric split sends
+NaN by missing_left and otherwise ``v <= thr32`` left; a categorical split
+sends NaN, ``v < 0`` and ``v >= 256`` by missing_left and otherwise
+``trunc(v)`` left iff its bit is set.
 """
 from __future__ import annotations
 
@@ -70,6 +98,11 @@ WALK_MAX_DEPTH = 64       # step bound of one walk
 WALK_MAX_GROUPS = 1024    # group bitset: 16 u64 words per sample in LDS
 WALK_MAX_FEATURES = 4096  # x row: 16 KiB of LDS
 WALK_MAX_RECORDS = 2**31 - 1
+# routed walk record [2]: flags above the group
+WALK_GROUP_MASK = 0xFFFF
+WALK_FLAG_MISSING_LEFT = 1 << 30
+WALK_FLAG_CATEGORICAL = 1 << 29
+CAT_CODES = 256           # category codes a bitset row holds
 
 ACT_CODE = {"none": 0, "sigmoid": 1, "softmax": 2}
 
@@ -126,6 +159,11 @@ def pack_trees(params: dict, col_group, device) -> dict:
     n_trees = len(trees)
     feat = np.zeros((n_trees, ipad), dtype=np.int64)
     thr = np.full((n_trees, ipad), -np.inf)
+    routing = params.get("routing")
+    if routing is not None:
+        # pad slots: not missing-left, numeric, threshold -inf -> bit 0
+        mleft = np.zeros((n_trees, ipad), dtype=bool)
+        crow = np.full((n_trees, ipad), -1, dtype=np.int64)
     child = np.zeros((_child_rows(counts), 2), dtype=np.int64)
     meta = np.zeros((n_trees, 4), dtype=np.int32)
     leaves, grp_off, grp_id, grp_mask = [], [0], [], []
@@ -160,6 +198,9 @@ def pack_trees(params: dict, col_group, device) -> dict:
                 k = code[i]
                 feat[ti, k] = tr["feature"][i]
                 thr[ti, k] = tr["threshold"][i]
+                if routing is not None:
+                    mleft[ti, k] = tr["missing_left"][i]
+                    crow[ti, k] = tr["cat_row"][i]
                 child[coff + k, 1] = code[left[i]]
                 child[coff + k, 0] = code[right[i]]
             by_group: dict = {}
@@ -181,7 +222,13 @@ def pack_trees(params: dict, col_group, device) -> dict:
     def dev(a):
         return t.from_numpy(np.ascontiguousarray(a)).to(device)
 
+    extra = {}
+    if routing is not None:
+        extra = {"routed": True, "missing_left": dev(mleft), "cat_row": dev(crow),
+                 "cat_left": dev(_cat_rows(routing).astype(np.int64)),
+                 "categories": _category_tensors(routing, device)}
     return {
+        **extra,
         "n_trees": n_trees, "n_out": n_out, "leaf_mode": 1 if vector else 0,
         "max_internal": int(max(counts)),
         "feat": dev(feat), "thr": dev(thr),
@@ -196,12 +243,50 @@ def pack_trees(params: dict, col_group, device) -> dict:
     }
 
 
+def _cat_rows(routing: dict) -> np.ndarray:
+    """(max(C, 1), 8) uint32: the bitset table, never empty, so that a
+    clamped row index always names a row."""
+    cat_left = np.asarray(routing["cat_left"], dtype=np.uint32).reshape(-1, 8)
+    if cat_left.shape[0] == 0:
+        cat_left = np.zeros((1, 8), dtype=np.uint32)
+    return cat_left
+
+
+def _category_tensors(routing: dict, device) -> dict:
+    import torch as t
+
+    return {int(f): t.from_numpy(np.asarray(c, dtype=np.float32)).to(device)
+            for f, c in sorted(routing["categories"].items())}
+
+
+def encode_rows(pack: dict, rows):
+    """float32 rows as the nodes of a routed pack see them: every feature
+    with known categories is replaced by the index of its value among them,
+    or NaN when it is not there (one ``searchsorted`` per such feature).
+    A pack without routing gets the float32 rows themselves."""
+    import torch as t
+
+    x = rows.float()
+    cats = pack.get("categories")
+    if not cats:
+        return x.contiguous()
+    x = x.clone()
+    for f, c in cats.items():
+        v = x[:, f].contiguous()
+        k = t.searchsorted(c, v).clamp_(max=c.shape[0] - 1)
+        x[:, f] = t.where(c[k] == v, k.to(v.dtype), t.full_like(v, float("nan")))
+    return x.contiguous()
+
+
 def decision_bits(pack: dict, rows):
     """(R, T) int64: bit i of [r, t] is ``float64(float32(rows[r, feat_i]))
     <= thr_i`` for internal node i of tree t — sklearn's comparison rule,
-    evaluated in torch on the device of ``rows``."""
+    evaluated in torch on the device of ``rows``. A routed pack encodes the
+    rows and applies the routing rule of the module docstring instead."""
     import torch as t
 
+    if pack.get("routed"):
+        return _decision_bits_routed(pack, rows)
     feat, thr = pack["feat"], pack["thr"]
     n_trees, ipad = feat.shape
     x = rows.float().double()
@@ -213,6 +298,34 @@ def decision_bits(pack: dict, rows):
         xs = x[lo : lo + step]
         go_left = xs[:, flat].view(-1, n_trees, ipad) <= thr[None]
         # disjoint bits: the wrapping int64 sum is the OR, bit 63 included
+        out[lo : lo + step] = (go_left.to(t.int64) << shifts).sum(dim=-1)
+    return out
+
+
+def _decision_bits_routed(pack: dict, rows):
+    import torch as t
+
+    feat, thr = pack["feat"], pack["thr"]
+    mleft, crow, cat_left = pack["missing_left"], pack["cat_row"], pack["cat_left"]
+    is_cat = crow >= 0
+    any_cat = bool(is_cat.any())
+    n_trees, ipad = feat.shape
+    x = encode_rows(pack, rows).double()
+    shifts = t.arange(ipad, device=x.device, dtype=t.int64) % 64
+    out = t.empty(x.shape[0], n_trees, dtype=t.int64, device=x.device)
+    step = max(1, (1 << 23) // (n_trees * ipad))
+    flat = feat.reshape(-1)
+    for lo in range(0, x.shape[0], step):
+        v = x[lo : lo + step][:, flat].view(-1, n_trees, ipad)
+        nan = v != v
+        go_left = t.where(nan, mleft[None], v <= thr[None])
+        if any_cat:
+            missing = nan | (v < 0) | (v >= CAT_CODES)
+            c = t.where(missing, t.zeros_like(v), v).long()      # truncates
+            word = cat_left[crow.clamp(min=0)[None].expand_as(c), c >> 5]
+            bit = ((word >> (c & 31)) & 1) != 0
+            go_left = t.where(is_cat[None],
+                              t.where(missing, mleft[None], bit), go_left)
         out[lo : lo + step] = (go_left.to(t.int64) << shifts).sum(dim=-1)
     return out
 
@@ -264,6 +377,7 @@ def pack_trees_walk(params: dict, col_group, device) -> dict:
     trees = params["trees"]
     col_group = np.asarray(col_group, dtype=np.int64)
     vector = params["out_col"] is None
+    routing = params.get("routing")
     nodes, roots, leaves = [], [], []
     off = n_leaf = max_depth = 0
     for ti, tr in enumerate(trees):
@@ -285,7 +399,16 @@ def pack_trees_walk(params: dict, col_group, device) -> dict:
                      else value.astype(np.float32).view(np.int32))
         rec[:, 0] = np.where(internal, thr32.view(np.int32), leaf_bits)
         rec[:, 1] = np.where(internal, feat, -1)
-        rec[:, 2] = np.where(internal, col_group[feat],
+        group = col_group[feat]
+        if routing is not None:
+            crow = np.asarray(tr["cat_row"], dtype=np.int64)[order]
+            cat = internal & (crow >= 0)
+            mleft = internal & np.asarray(tr["missing_left"], dtype=bool)[order]
+            rec[:, 0] = np.where(cat, crow, rec[:, 0])
+            group = (group & WALK_GROUP_MASK) \
+                | np.where(mleft, WALK_FLAG_MISSING_LEFT, 0) \
+                | np.where(cat, WALK_FLAG_CATEGORICAL, 0)
+        rec[:, 2] = np.where(internal, group,
                              0 if vector else int(params["out_col"][ti]))
         rec[:, 3] = np.where(internal, pos[np.maximum(right[order], 0)], leaf_row)
         nodes.append(rec)
@@ -297,7 +420,13 @@ def pack_trees_walk(params: dict, col_group, device) -> dict:
     def dev(a):
         return t.from_numpy(np.ascontiguousarray(a)).to(device)
 
+    extra = {}
+    if routing is not None:
+        extra = {"routed": True,
+                 "cat_left": dev(_cat_rows(routing).view(np.int32)),
+                 "categories": _category_tensors(routing, device)}
     return {
+        **extra,
         "n_trees": len(trees), "n_out": int(params["n_out"]),
         "leaf_mode": 1 if vector else 0, "max_depth": int(max_depth),
         "nodes": dev(np.concatenate(nodes)),
@@ -311,7 +440,15 @@ def pack_trees_walk(params: dict, col_group, device) -> dict:
 
 def fused_predict_walk(ext, pack: dict, masks, vmap, x, bg, wbg, ey):
     """Launch ``fused_predict_trees_walk`` with the packed tables; ``x``
-    (B, D) and ``bg`` (N, D) are the float32 rows themselves."""
+    (B, D) and ``bg`` (N, D) are the float32 rows themselves, for a routed
+    pack the rows that ``encode_rows`` returns."""
+    if pack.get("routed"):
+        ext.fused_predict_trees_walk(
+            masks, vmap, x, bg, pack["nodes"], pack["roots"], pack["leaves"],
+            pack["base"], pack["scale"], wbg, ey, pack["act"],
+            pack["leaf_mode"], pack["max_depth"], cat_left=pack["cat_left"],
+        )
+        return ey
     ext.fused_predict_trees_walk(
         masks, vmap, x, bg, pack["nodes"], pack["roots"], pack["leaves"],
         pack["base"], pack["scale"], wbg, ey, pack["act"], pack["leaf_mode"],

@@ -160,7 +160,8 @@ def load_model(path: str = None):
     """Unpickle a predictor; sklearn LogisticRegression is wrapped into the
     native LinearPredictor and sklearn MLPClassifier / MLPRegressor into
     the native MLPPredictor, and sklearn decision trees, forests and
-    gradient boosting into the native TreeEnsemblePredictor, and sklearn
+    gradient boosting into the native TreeEnsemblePredictor (histogram
+    gradient boosting into RoutedTreeEnsemblePredictor), and sklearn
     kernel SVMs / kernel ridge into the native KernelMachinePredictor, so
     the fused GPU paths apply (reference ``load_model``, utils.py:137-157)."""
     import pickle
@@ -184,6 +185,12 @@ def load_model(path: str = None):
     coefs = getattr(obj, "coefs_", None)
     if coefs is not None and hasattr(obj, "out_activation_"):
         return _wrap_sklearn_mlp(obj)
+    if type(obj).__name__.startswith("HistGradientBoosting") \
+            and type(obj).__module__.startswith("sklearn.ensemble"):
+        # missing-value and categorical routing: the routed tree predictor
+        from ..models.predictors import RoutedTreeEnsemblePredictor
+
+        return RoutedTreeEnsemblePredictor.from_sklearn(obj)
     if type(obj).__module__.startswith(("sklearn.tree", "sklearn.ensemble")) \
             and (hasattr(obj, "tree_") or hasattr(obj, "estimators_")):
         # raises TypeError with the reason for an unsupported tree model
