@@ -91,6 +91,11 @@ extern "C" int launch_wls_solve_packed(
     const float* total, const int64_t* vidx, float* phi_full, int B, int S,
     int M, int n_out, int G, hipStream_t stream);
 
+extern "C" int launch_varying_probe(
+    const float* X, const float* bg_min, const float* bg_max,
+    const float* tol_min, const float* tol_max, const int64_t* col_group,
+    int64_t* keys, int64_t* probe, int B, int D, int G, hipStream_t stream);
+
 // mlp_kernels.hip
 extern "C" int launch_fused_predict_mlp(
     const uint8_t* masks, const void* xp1, const void* bgp1n,
@@ -345,6 +350,33 @@ void wls_solve_packed(
         G, current_stream());
     TORCH_CHECK(rc == 0, "wls_solve_packed: unsupported shape (2<=M<=G, "
                          "(M-1)+n_out<=16)");
+}
+
+void varying_probe(
+    torch::Tensor X, torch::Tensor bg_min, torch::Tensor bg_max,
+    torch::Tensor tol_min, torch::Tensor tol_max, torch::Tensor col_group,
+    int64_t n_groups, torch::Tensor keys, torch::Tensor probe) {
+    CHECK_DEV(X); CHECK_DEV(bg_min); CHECK_DEV(bg_max); CHECK_DEV(tol_min);
+    CHECK_DEV(tol_max); CHECK_DEV(col_group); CHECK_DEV(keys); CHECK_DEV(probe);
+    CHECK_F32(X); CHECK_F32(bg_min); CHECK_F32(bg_max); CHECK_F32(tol_min);
+    CHECK_F32(tol_max); CHECK_I64(col_group); CHECK_I64(keys); CHECK_I64(probe);
+    TORCH_CHECK(X.dim() == 2, "X must be (B,D)");
+    const int64_t B = X.size(0), D = X.size(1);
+    TORCH_CHECK(B >= 1 && D >= 1 && B <= 0x7fffffffLL && D <= 0x7fffffffLL,
+                "X must be (B,D) with B, D >= 1");
+    TORCH_CHECK(bg_min.numel() == D && bg_max.numel() == D
+                && tol_min.numel() == D && tol_max.numel() == D
+                && col_group.numel() == D,
+                "bg_min, bg_max, tol_min, tol_max, col_group must be (D,)");
+    TORCH_CHECK(keys.numel() == B, "keys must be (B,)");
+    TORCH_CHECK(probe.numel() == 2, "probe must be (2,)");
+    int rc = launch_varying_probe(
+        X.data_ptr<float>(), bg_min.data_ptr<float>(), bg_max.data_ptr<float>(),
+        tol_min.data_ptr<float>(), tol_max.data_ptr<float>(),
+        col_group.data_ptr<int64_t>(), keys.data_ptr<int64_t>(),
+        probe.data_ptr<int64_t>(), (int)B, (int)D, (int)n_groups,
+        current_stream());
+    TORCH_CHECK(rc == 0, "varying_probe: unsupported shape (1 <= n_groups <= 62)");
 }
 
 void fused_predict_bf16(
@@ -813,6 +845,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("packed"), pybind11::arg("kw"), pybind11::arg("ey_adj"),
           pybind11::arg("total"), pybind11::arg("vidx"),
           pybind11::arg("phi_full"));
+    m.def("varying_probe", &varying_probe,
+          "varying-pattern probe (K1p): per-instance group bit keys and "
+          "[all(keys == keys[0]), keys[0]] in two launches, no host sync",
+          pybind11::arg("X"), pybind11::arg("bg_min"), pybind11::arg("bg_max"),
+          pybind11::arg("tol_min"), pybind11::arg("tol_max"),
+          pybind11::arg("col_group"), pybind11::arg("n_groups"),
+          pybind11::arg("keys"), pybind11::arg("probe"));
     m.def("fill_random_masks", &fill_random_masks,
           "Philox coalition sampling (K2)");
     m.def("fused_predict_linear", &fused_predict_linear,

@@ -3,6 +3,8 @@
 // Native implementation of the numeric inner loop the reference delegates to
 // shap 0.35.0 (reference call site explainers/kernel_shap.py:250; kernel
 // inventory SURVEY.md §2.4):
+//   K1p varying_probe           — per-instance varying-group bit keys and
+//                                 [all keys equal, keys[0]] in two launches
 //   K2  fill_random_masks       — counter-based (Philox4x32-10) coalition
 //                                 sampling, complement-paired; 8 waves per
 //                                 instance with ballot/prefix row allocation
@@ -59,6 +61,7 @@
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <type_traits>
 
 #define WAVE 64
 
@@ -2724,11 +2727,56 @@ extern "C" int launch_fused_predict_linear_packed(
     }
 }
 
-// K7p: wls_solve_mfma_kernel with the kernel weights read as the (S,) vector
-// every instance shares, and the result written straight into
-// phi_full (B, G, n_out): group vidx[k] receives phi[k], every other group of
-// the row receives 0.  Gram, Cholesky and solve arithmetic are unchanged.
-__global__ __launch_bounds__(256)
+// K7p: the arithmetic of wls_solve_mfma_kernel, entry by entry and in the
+// same order (results are bit-identical to it), with the kernel weights read
+// as the (S,) vector every instance shares and the result written straight
+// into phi_full (B, G, n_out): group vidx[k] receives phi[k], every other
+// group of the row receives 0.  What differs is where the values travel:
+//   * one wave per instance (64-thread blocks): every block of a CU is
+//     resident at once and no step waits on another wave
+//   * lane (r, q) = (lane & 15, lane >> 4) loads sample 4r + q of a 64-sample
+//     block, so the four samples of MFMA j sit in lane j of the four 16-lane
+//     rows and reach the operands by DPP row broadcast: no LDS staging, and
+//     the next block's words, weights and ey are requested before this
+//     block's MFMAs
+//   * the four accumulators of the former four waves (64-sample block w of
+//     each 256-sample chunk) stay separate and are summed in the same order;
+//     MFMAs past the end of S (all-zero operands) are not issued
+//   * Cholesky right-looking with row r in the registers of lane r, the
+//     pivot column broadcast by DPP; both triangular solves run from
+//     registers with the L entries broadcast the same way, every entry's
+//     subtractions in the former order (t ascending, then the division).
+//     Rows and columns >= M-1 are padded with the identity.
+template <int J>
+__device__ __forceinline__ float dpp_row_bcast(float v) {   // lane J of each 16-lane row
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
+        0, __builtin_bit_cast(int, v), 0x150 + J, 0xF, 0xF, true));
+}
+template <int J>
+__device__ __forceinline__ uint32_t dpp_row_bcast_u(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x150 + J, 0xF, 0xF, true);
+}
+
+template <int I, int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        static_for<I + 1, N>(f);
+    }
+}
+
+#define WLSP_MAXM 15       // (M-1) <= 15
+
+template <int NOUT>
+struct WlsSample {         // one lane's sample of a 64-sample block, as loaded
+    uint32_t bits;         // (from a clamped index: ok says whether it counts,
+    float w;               // applied where the values are consumed, so that
+    float e[NOUT];         // no wait sits between the request and the MFMAs
+    bool ok;               // of the block before)
+};
+
+template <int NOUT>        // n_out <= NOUT
+__global__ __launch_bounds__(64)
 void wls_solve_packed_kernel(
     const uint64_t* __restrict__ packed, // (B, S)
     const float* __restrict__ kw,        // (S,)
@@ -2740,116 +2788,157 @@ void wls_solve_packed_kernel(
 {
     const int b = blockIdx.x;
     if (b >= B) return;
-    const int tid = threadIdx.x;
-    const int lane = tid & (WAVE - 1);
-    const int wv = tid >> 6;
-    const int mm = M - 1;
-    const int cols = mm + n_out;         // <= 16
+    const int lane = threadIdx.x;
+    const int arow = lane & 15;
+    const int akk = lane >> 4;
+    const int mm = M - 1;                // <= 15
 
-    __shared__ uint64_t pk[WLS_CHUNK];
-    __shared__ float wch[WLS_CHUNK];
-    __shared__ float eych[WLS_CHUNK][WLS_MAX_NOUT];
-    __shared__ float tileA[4][16][17];
-    __shared__ float A[16 * 16];
-    __shared__ float rhs[16 * WLS_MAX_NOUT];
-    __shared__ float tot_s[WLS_MAX_NOUT];
-    __shared__ float phi_s[17 * WLS_MAX_NOUT];
-    __shared__ int g_s[17];
+    __shared__ float As[16][17];         // Gram | rhs tile, (i, j)
+    __shared__ float phi_s[16][NOUT];
+    __shared__ int g_s[16];
 
-    if (tid < n_out) tot_s[tid] = total[(size_t)b * n_out + tid];
-    if (tid < M) g_s[tid] = (int)vidx[tid];
-    __syncthreads();
+    float tot[NOUT];
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o)
+        tot[o] = o < n_out ? total[(size_t)b * n_out + o] : 0.0f;
+    if (lane < M) g_s[lane] = (int)vidx[lane];
 
     const uint64_t* pbase = packed + (size_t)b * S;
     const float* eyb = ey_adj + (size_t)b * S * n_out;
+    const int slot = 4 * arow + akk;     // this lane's sample within a block
+    const bool is_a = arow < mm;
+    const int osel = arow - mm;          // output carried by B column arow
 
-    const int arow = lane & 15;
-    const int akk = lane >> 4;
+    auto load = [&](int base) __attribute__((always_inline)) {
+        WlsSample<NOUT> s;
+        s.ok = base + slot < S;
+        const int idx = min(base + slot, S - 1);   // no branch around a load
+        s.bits = (uint32_t)pbase[idx];             // M <= 16: low word only
+        s.w = kw[idx];
+#pragma unroll
+        for (int o = 0; o < NOUT; ++o)
+            s.e[o] = eyb[(size_t)idx * n_out + min(o, n_out - 1)];
+        return s;
+    };
 
-    f32x4 acc = (f32x4){0, 0, 0, 0};
-
-    for (int c0 = 0; c0 < S; c0 += WLS_CHUNK) {
-        const int clen = min(WLS_CHUNK, S - c0);
-        // each wave stages exactly the samples it consumes (see
-        // wls_solve_mfma_kernel): no barrier, only an LDS wait
-        if (tid < clen) {
-            uint64_t bits = pbase[c0 + tid];
-            pk[tid] = bits;
-            wch[tid] = kw[c0 + tid];
-            float mlast = (float)((bits >> (M - 1)) & 1ull);
-            for (int o = 0; o < n_out; ++o)
-                eych[tid][o] = eyb[(size_t)(c0 + tid) * n_out + o] - mlast * tot_s[o];
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const int base = wv * 64;
-        for (int ks = 0; ks < 64; ks += 4) {
-            int t = base + ks + akk;
-            float a = 0.0f, bv = 0.0f;
-            if (t < clen) {
-                uint64_t bits = pk[t];
-                float ml = (float)((bits >> (M - 1)) & 1ull);
-                float w = wch[t];
-                if (arow < mm) a = (float)((bits >> arow) & 1ull) - ml;
-                if (arow < mm) bv = w * ((float)((bits >> arow) & 1ull) - ml);
-                else if (arow < cols) bv = w * eych[t][arow - mm];
+    // 64 samples = up to 16 MFMAs into one accumulator; rem = samples left
+    auto gram_block = [&](f32x4& acc, const WlsSample<NOUT>& raw, int rem) __attribute__((always_inline)) {
+        WlsSample<NOUT> s;
+        s.bits = raw.ok ? raw.bits : 0u;
+        s.w = raw.ok ? raw.w : 0.0f;
+        const float ml = (float)((s.bits >> mm) & 1u);
+        float wey[NOUT];
+#pragma unroll
+        for (int o = 0; o < NOUT; ++o)
+            wey[o] = o < n_out ? s.w * (raw.e[o] - ml * tot[o]) : 0.0f;
+        static_for<0, 16>([&](auto jc) __attribute__((always_inline)) {
+            constexpr int j = decltype(jc)::value;
+            if (4 * j < rem) {           // wave-uniform
+                const uint32_t bb = dpp_row_bcast_u<j>(s.bits);
+                const float ww = dpp_row_bcast<j>(s.w);
+                float es = 0.0f;
+#pragma unroll
+                for (int o = 0; o < NOUT; ++o) {
+                    const float t = dpp_row_bcast<j>(wey[o]);
+                    es = (osel == o) ? t : es;
+                }
+                const float d = (float)((int)((bb >> arow) & 1u)
+                                        - (int)((bb >> mm) & 1u));
+                const float a = is_a ? d : 0.0f;
+                const float bv = is_a ? ww * d : es;
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
             }
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
-        }
+        });
+    };
+
+    f32x4 acc[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) acc[w] = (f32x4){0, 0, 0, 0};
+
+    WlsSample<NOUT> cur = load(0);
+    for (int c0 = 0; c0 < S; c0 += WLS_CHUNK) {
+        static_for<0, 4>([&](auto wc) __attribute__((always_inline)) {
+            constexpr int w = decltype(wc)::value;
+            const int base = c0 + w * 64;
+            if (base < S) {              // wave-uniform
+                const WlsSample<NOUT> nxt = load(base + 64);
+                gram_block(acc[w], cur, S - base);
+                cur = nxt;
+            }
+        });
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-        tileA[wv][(lane >> 4) * 4 + r][lane & 15] = acc[r];
-    __syncthreads();
-    for (int idx = tid; idx < 16 * 16; idx += 256) {
-        int i = idx / 16, j = idx % 16;
-        float v = tileA[0][i][j] + tileA[1][i][j] + tileA[2][i][j] + tileA[3][i][j];
-        if (j < mm) A[i * mm + j] = v;
-        else if (j < cols && i < mm) rhs[i * n_out + (j - mm)] = v;
-    }
+        As[akk * 4 + r][arow] = ((acc[0][r] + acc[1][r]) + acc[2][r]) + acc[3][r];
     __syncthreads();
 
-    if (tid == 0) {
-        for (int k = 0; k < mm; ++k) {
-            float d = A[k * mm + k];
-            for (int t = 0; t < k; ++t) d -= A[k * mm + t] * A[k * mm + t];
-            d = sqrtf(fmaxf(d, 1e-20f));
-            A[k * mm + k] = d;
-            float inv = 1.0f / d;
-            for (int r = k + 1; r < mm; ++r) {
-                float v = A[r * mm + k];
-                for (int t = 0; t < k; ++t) v -= A[r * mm + t] * A[k * mm + t];
-                A[r * mm + k] = v * inv;
-            }
-        }
+    // lane r (of every 16-lane row) takes row r of the Gram block
+    float L[WLSP_MAXM];
+#pragma unroll
+    for (int c = 0; c < WLSP_MAXM; ++c) {
+        const float v = As[arow][c];
+        L[c] = (arow < mm && c < mm) ? v : (arow == c ? 1.0f : 0.0f);
     }
-    __syncthreads();
-    if (tid < n_out) {
-        const int o = tid;
-        float y[16];
-        for (int i = 0; i < mm; ++i) {
-            float v = rhs[i * n_out + o];
-            for (int t = 0; t < i; ++t) v -= A[i * mm + t] * y[t];
-            y[i] = v / A[i * mm + i];
-        }
-        float w[16];
-        float sumw = 0.0f;
-        for (int i = mm - 1; i >= 0; --i) {
+    static_for<0, WLSP_MAXM>([&](auto kc) __attribute__((always_inline)) {
+        constexpr int k = decltype(kc)::value;
+        const float d = sqrtf(fmaxf(dpp_row_bcast<k>(L[k]), 1e-20f));
+        const float inv = 1.0f / d;
+        const float lk = L[k] * inv;     // L[r][k], meaningful for r > k
+        L[k] = (arow == k) ? d : lk;
+        static_for<k + 1, WLSP_MAXM>([&](auto cc) __attribute__((always_inline)) {
+            constexpr int c = decltype(cc)::value;
+            L[c] = fmaf(-lk, dpp_row_bcast<c>(lk), L[c]);
+        });
+    });
+
+    // 16-lane row q solves outputs q, q + 4; every lane of the row computes
+    // the whole vector
+#pragma unroll 1
+    for (int o0 = 0; o0 < NOUT; o0 += 4) {
+        const int o = o0 + akk;
+        const bool live = o < n_out;
+        const float r_own = (live && arow < mm) ? As[arow][mm + (live ? o : 0)] : 0.0f;
+        float y[WLSP_MAXM], wv[WLSP_MAXM];
+        static_for<0, WLSP_MAXM>([&](auto ic) __attribute__((always_inline)) {
+            constexpr int i = decltype(ic)::value;
+            float v = dpp_row_bcast<i>(r_own);
+            static_for<0, i>([&](auto tc) __attribute__((always_inline)) {
+                constexpr int t = decltype(tc)::value;
+                v = fmaf(-dpp_row_bcast<i>(L[t]), y[t], v);
+            });
+            y[i] = v / dpp_row_bcast<i>(L[i]);
+        });
+        static_for<0, WLSP_MAXM>([&](auto ic) __attribute__((always_inline)) {
+            constexpr int i = WLSP_MAXM - 1 - decltype(ic)::value;
             float v = y[i];
-            for (int t = i + 1; t < mm; ++t) v -= A[t * mm + i] * w[t];
-            w[i] = v / A[i * mm + i];
+            static_for<i + 1, WLSP_MAXM>([&](auto tc) __attribute__((always_inline)) {
+                constexpr int t = decltype(tc)::value;
+                v = fmaf(-dpp_row_bcast<t>(L[i]), wv[t], v);
+            });
+            wv[i] = v / dpp_row_bcast<i>(L[i]);
+        });
+        float sumw = 0.0f;
+#pragma unroll
+        for (int i = 0; i < WLSP_MAXM; ++i) sumw += wv[i];   // pad rows add 0
+        if (live) {
+            float mine = 0.0f;           // lane r keeps w[r]
+#pragma unroll
+            for (int i = 0; i < WLSP_MAXM; ++i) mine = (arow == i) ? wv[i] : mine;
+            float to = 0.0f;
+#pragma unroll
+            for (int oo = 0; oo < NOUT; ++oo) to = (o == oo) ? tot[oo] : to;
+            if (arow < mm) phi_s[arow][o] = mine;
+            if (arow == mm) phi_s[mm][o] = to - sumw;
         }
-        for (int i = 0; i < mm; ++i) sumw += w[i];
-        for (int i = 0; i < mm; ++i) phi_s[i * n_out + o] = w[i];
-        phi_s[(M - 1) * n_out + o] = tot_s[o] - sumw;
     }
     __syncthreads();
     // every element of the row is written exactly once
     float* prow = phi_full + (size_t)b * G * n_out;
-    for (int idx = tid; idx < G * n_out; idx += 256) {
+    for (int idx = lane; idx < G * n_out; idx += 64) {
         const int g = idx / n_out, o = idx % n_out;
         float v = 0.0f;
         for (int k = 0; k < M; ++k)
-            if (g_s[k] == g) v = phi_s[k * n_out + o];
+            if (g_s[k] == g) v = phi_s[k][o];
         prow[idx] = v;
     }
 }
@@ -2863,7 +2952,92 @@ extern "C" int launch_wls_solve_packed(
             || (M - 1) + n_out > 16)
         return -1;
     if (B <= 0) return 0;
-    wls_solve_packed_kernel<<<dim3(B), dim3(256), 0, stream>>>(
-        packed, kw, ey_adj, total, vidx, phi_full, B, S, M, n_out, G);
+#define KSHAP_WLSP(NO) \
+    wls_solve_packed_kernel<NO><<<dim3(B), dim3(64), 0, stream>>>( \
+        packed, kw, ey_adj, total, vidx, phi_full, B, S, M, n_out, G)
+    if (n_out == 1) KSHAP_WLSP(1);
+    else if (n_out == 2) KSHAP_WLSP(2);
+    else if (n_out <= 4) KSHAP_WLSP(4);
+    else KSHAP_WLSP(8);
+#undef KSHAP_WLSP
+    return 0;
+}
+
+// ========================================================================= //
+// K1p: varying-pattern probe.  One question per call: which groups vary for
+// each instance, and do all instances share one pattern?
+//   keys[b]  bit g set iff some column j of group g has x[b,j] not close to
+//            the background extremes:
+//              close(j) = |bg_min[j] - x| <= tol_min[j] && |bg_max[j] - x| <= tol_max[j]
+//            (tolerances precomputed at fit; NaN compares false = varying)
+//   probe    [all(keys == keys[0]), keys[0]]
+// Two launches, integers only, plain stores: every word of keys and probe is
+// written by the call that reads it, so no buffer has to be cleared between
+// calls and nothing is handed from block to block inside a launch.
+// ========================================================================= //
+
+// One wave per instance: lanes stride over the D columns (coalesced row
+// reads), OR their group bits, and a butterfly leaves the key in every lane.
+__global__ __launch_bounds__(256)
+void varying_keys_kernel(
+    const float* __restrict__ X,          // (B, D)
+    const float* __restrict__ bg_min,     // (D,)
+    const float* __restrict__ bg_max,     // (D,)
+    const float* __restrict__ tol_min,    // (D,)
+    const float* __restrict__ tol_max,    // (D,)
+    const int64_t* __restrict__ col_group,  // (D,)
+    int64_t* __restrict__ keys,           // (B,)
+    int B, int D)
+{
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int b = blockIdx.x * (blockDim.x / WAVE) + (threadIdx.x >> 6);
+    if (b >= B) return;                   // wave-uniform
+    const float* xr = X + (size_t)b * D;
+    uint64_t bits = 0ull;
+    for (int j = lane; j < D; j += WAVE) {
+        const float x = xr[j];
+        const bool cmin = fabsf(__fsub_rn(bg_min[j], x)) <= tol_min[j];
+        const bool cmax = fabsf(__fsub_rn(bg_max[j], x)) <= tol_max[j];
+        const int64_t g = col_group[j];
+        if (!(cmin && cmax) && g >= 0 && g < 64) bits |= 1ull << g;
+    }
+    uint32_t lo = (uint32_t)bits, hi = (uint32_t)(bits >> 32);
+#pragma unroll
+    for (int off = 1; off < WAVE; off <<= 1) {
+        lo |= (uint32_t)__shfl_xor((int)lo, off, WAVE);
+        hi |= (uint32_t)__shfl_xor((int)hi, off, WAVE);
+    }
+    if (lane == 0) keys[b] = (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// One block: any(keys != keys[0]) over the B keys the first launch wrote.
+__global__ __launch_bounds__(1024)
+void varying_probe_reduce_kernel(
+    const int64_t* __restrict__ keys,     // (B,)
+    int64_t* __restrict__ probe,          // (2,)
+    int B)
+{
+    const int64_t k0 = keys[0];
+    int differs = 0;
+    for (int i = threadIdx.x; i < B; i += blockDim.x)
+        differs |= (keys[i] != k0);
+    differs = __syncthreads_or(differs);
+    if (threadIdx.x == 0) {
+        probe[0] = differs ? 0 : 1;
+        probe[1] = k0;
+    }
+}
+
+extern "C" int launch_varying_probe(
+    const float* X, const float* bg_min, const float* bg_max,
+    const float* tol_min, const float* tol_max, const int64_t* col_group,
+    int64_t* keys, int64_t* probe, int B, int D, int G, hipStream_t stream)
+{
+    if (B < 1 || D < 1 || G < 1 || G > 62) return -1;
+    const int wpb = 256 / WAVE;
+    varying_keys_kernel<<<dim3((B + wpb - 1) / wpb), dim3(256), 0, stream>>>(
+        X, bg_min, bg_max, tol_min, tol_max, col_group, keys, B, D);
+    varying_probe_reduce_kernel<<<dim3(1), dim3(1024), 0, stream>>>(
+        keys, probe, B);
     return 0;
 }
