@@ -75,6 +75,15 @@ class KernelConfig:
     # fp64: full-double verification mode (linear predictors) — the
     # reference's numpy-fp64 arithmetic, used by bench.py's self-check.
     predict_dtype: str = "fp32"  # fp32 | bf16x2 | bf16 | fp64
+    # matrix instruction of the packed linear predict (fp32 results either
+    # way).  split: bf16 matrix cores on an exact three-piece bf16 split of
+    # the fp32 operands (mask bits x pieces are exact products, fp32
+    # accumulation), eligible for the sigmoid-type activations with at most
+    # 12 varying groups; other shapes take the f32 MFMA silently.  auto:
+    # split where eligible.  Non-finite weights or inputs are outside the
+    # split path's contract: inf - inf in the split gives NaN where the f32
+    # MFMA gives a saturated probability.
+    packed_mma: str = "auto"  # auto | f32 | split
     synth_chunk_rows: int = 1 << 21  # ~0.5 GB synth tiles: +15% on mlp vs 2^19
     # l1_reg selection on GPU batches: True = device Gram + batched torch
     # LARS (core.lars), False = per-instance host sklearn (the CPU oracle's

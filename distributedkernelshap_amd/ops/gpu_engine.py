@@ -1086,6 +1086,16 @@ class GpuKernelShap:
             self._enum_cache[key] = ent
         return ent
 
+    def _packed_mma(self):
+        """KernelConfig.packed_mma as the binding's ``mma`` argument."""
+        mode = self.engine.kernels.packed_mma
+        try:
+            return {"auto": -1, "f32": 0, "split": 1}[mode]
+        except KeyError:
+            raise ValueError(
+                f"packed_mma must be 'auto', 'f32' or 'split', got {mode!r}"
+            ) from None
+
     def _packed_pipeline(self, X_dev, plan, vidx_t, ids_dev, phi_full,
                          timer=None):
         """X_dev (b, D) -> phi_full (b, n_groups, n_out), every element
@@ -1114,7 +1124,7 @@ class GpuKernelShap:
         ey = self._buf("ey", (b, s, self.n_out))
         self.ext.fused_predict_linear_packed(
             packed, diff, c["base"], c["wbg"], ey, c["act"], c["link"],
-            c["lfnull"],
+            c["lfnull"], self._packed_mma(),
         )
         if timer is not None:
             timer.mark("predict")

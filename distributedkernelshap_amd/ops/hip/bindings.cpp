@@ -84,7 +84,7 @@ extern "C" int launch_linear_prepare(
 extern "C" int launch_fused_predict_linear_packed(
     const uint64_t* packed, const float* diff, const float* base,
     const float* wbg, const float* lfnull, float* ey, int B, int S, int Mpad,
-    int Npad, int n_out, int act, int link, hipStream_t stream);
+    int Npad, int n_out, int act, int link, hipStream_t stream, int mma);
 
 extern "C" int launch_wls_solve_packed(
     const uint64_t* packed, const float* kw, const float* ey_adj,
@@ -297,7 +297,7 @@ void linear_prepare(
 void fused_predict_linear_packed(
     torch::Tensor packed, torch::Tensor diff, torch::Tensor base,
     torch::Tensor wbg, torch::Tensor ey, int64_t act, int64_t link,
-    c10::optional<torch::Tensor> lfnull) {
+    c10::optional<torch::Tensor> lfnull, int64_t mma) {
     CHECK_DEV(packed); CHECK_DEV(diff); CHECK_DEV(base); CHECK_DEV(wbg); CHECK_DEV(ey);
     CHECK_I64(packed); CHECK_F32(diff); CHECK_F32(base); CHECK_F32(wbg); CHECK_F32(ey);
     TORCH_CHECK(packed.dim() == 2 && diff.dim() == 4 && ey.dim() == 3
@@ -318,11 +318,13 @@ void fused_predict_linear_packed(
     }
     TORCH_CHECK(link == 0 || (link == 1 && lf != nullptr),
                 "link must be 0, or 1 with lfnull given");
+    TORCH_CHECK(mma >= -1 && mma <= 1,
+                "mma must be -1 (auto), 0 (fp32 MFMA) or 1 (split bf16 MFMA)");
     int rc = launch_fused_predict_linear_packed(
         reinterpret_cast<const uint64_t*>(packed.data_ptr<int64_t>()),
         diff.data_ptr<float>(), base.data_ptr<float>(), wbg.data_ptr<float>(),
         lf, ey.data_ptr<float>(), B, S, Mpad, Npad, n_out, (int)act, (int)link,
-        current_stream());
+        current_stream(), (int)mma);
     TORCH_CHECK(rc == 0, "fused_predict_linear_packed: unsupported shape "
                          "(Mpad%4==0, Mpad<=64, Npad%16==0, Npad<=128, n_out in "
                          "{1,2,4}, operand images within 64 KiB of LDS)");
@@ -835,10 +837,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("link"));
     m.def("fused_predict_linear_packed", &fused_predict_linear_packed,
           "MFMA fused predict from packed mask words with the link fused into "
-          "the epilogue (K3p)",
+          "the epilogue (K3p); mma: -1 auto, 0 fp32 MFMA, 1 split-operand bf16 "
+          "MFMA (Mpad <= 12, act 1/3; other shapes take the fp32 MFMA path)",
           pybind11::arg("packed"), pybind11::arg("diff"), pybind11::arg("base"),
           pybind11::arg("wbg"), pybind11::arg("ey"), pybind11::arg("act"),
-          pybind11::arg("link") = 0, pybind11::arg("lfnull") = pybind11::none());
+          pybind11::arg("link") = 0, pybind11::arg("lfnull") = pybind11::none(),
+          pybind11::arg("mma") = -1);
     m.def("wls_solve_packed", &wls_solve_packed,
           "MFMA WLS solve with (S,) kernel weights, scattered into "
           "phi_full (B,G,n_out) through vidx (K7p)",

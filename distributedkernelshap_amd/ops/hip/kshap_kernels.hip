@@ -63,6 +63,8 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "split_bf16.h"
+
 #define WAVE 64
 
 // ------------------------------------------------------------------------- //
@@ -2404,6 +2406,29 @@ extern "C" int launch_linear_prepare(
 // link: 0 = ey - lfnull (or plain ey when lfnull is null), 1 = logit(clamp(
 // ey, 1e-7, 1-1e-7)) - lfnull with the logit as ln2*(log2 p - log2(1-p)) on
 // the hardware log (absolute error ~1e-7 * |log|).
+//
+// MMA = 1 (ACT 1 and 3, KS 1..3, i.e. Mpad <= 12) runs the same GEMM on the
+// bf16 matrix cores with fp32 results: the A operand is mask bits (0 and 1 are
+// exact in bf16) and every scaled fp32 diff/base value is split by truncation
+// into three bf16 pieces hi + mid + lo == v (split_bf16.h), so every product
+// is exact and the accumulation is fp32 as before.  Two
+// v_mfma_f32_16x16x32_bf16 per column tile; lane group q = lane>>4 owns
+// groups 3q..3q+2:
+//   first   k-slots 0-2 their hi, 3-5 their mid, slot 6 one piece of base[n]
+//           (q = 0,1,2 -> hi, mid, lo) against an A element of 1.0, slot 7 zero
+//   second  slots 0-2 the lo pieces, the rest zero
+// 32 matrix-pipe cycles per tile instead of 96, accumulators start from 0
+// (the base rides in a k-slot).  Both are the same instruction on purpose: a
+// narrower v_mfma_f32_16x16x16_bf16 for the lo pieces is scheduled by the
+// compiler directly behind the MFMA whose result it accumulates onto (no
+// wait states between different MFMA shapes) and then returned wrong sums
+// on gfx950 wherever fewer than three tiles separate the pair.  The B
+// fragments are built once per block, in lane order in LDS (two 16-byte
+// reads per lane and tile, conflict-free), and stay in registers across the
+// sub-tile loop while NT*OIMG <= 8.  Non-finite operands are outside this
+// path's contract (inf - inf in the split is NaN).
+
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 __device__ __forceinline__ float dpp_add_quad1(float v) {   // + lane^1
     return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
@@ -2422,7 +2447,7 @@ __device__ __forceinline__ float dpp_add_mirror(float v) {  // 16-lane mirror
         0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
 }
 
-template <int NOUT, int ACT, int NT, int KS>
+template <int NOUT, int ACT, int NT, int KS, int MMA>
 __global__ __launch_bounds__(256, 2)   // <= 256 registers: the accumulators
 void fused_predict_linear_packed_kernel(  // stay in VGPRs the VALU can read
     const uint64_t* __restrict__ packed, // (B, S) mask words
@@ -2438,6 +2463,11 @@ void fused_predict_linear_packed_kernel(  // stay in VGPRs the VALU can read
     constexpr int NPAD = NT * 16;
     constexpr int NSTRIDE = NPAD + ((16 - (NPAD & 31)) & 31);  // ≡16 mod 32
     constexpr bool SIG = (ACT == 1 || ACT == 3);
+    constexpr bool SPL = (MMA == 1);
+    static_assert(!SPL || (SIG && KS >= 1 && KS <= 3),
+                  "split path: sigmoid-type activations, Mpad <= 12");
+    // B fragments of the split path held in registers across the sub-tiles
+    constexpr bool BREG = SPL && (NT * OIMG <= 8);
     // accumulator tiles beyond 16 are processed in two column halves (as in
     // the u8 kernel) to bound the AGPR footprint
     constexpr int NHALF = (NT * OIMG > 16) ? 2 : 1;
@@ -2455,16 +2485,48 @@ void fused_predict_linear_packed_kernel(  // stay in VGPRs the VALU can read
     float* diff_lds = lds;                                   // OIMG*Mpad*NSTRIDE
     float* base_lds = diff_lds + OIMG * Mpad * NSTRIDE;      // OIMG*NPAD
     float* wbg_lds = base_lds + OIMG * NPAD;                 // NPAD
+    // split path: fragment (o, ct) of lane l at index (o*NT + ct)*64 + l
+    u32x4* bw_lds = (u32x4*)lds;                             // OIMG*NT*64
+    u32x4* bn_lds = bw_lds + OIMG * NT * 64;                 // OIMG*NT*64
+    if constexpr (SPL) wbg_lds = (float*)(bn_lds + OIMG * NT * 64);
 
     const float scale = SIG ? -1.44269504088896340736f : 1.0f;
     const float* dsrc = diff + (size_t)b * OIMG * Mpad * NPAD;
-    for (int idx = tid; idx < OIMG * Mpad * NPAD; idx += 256) {
-        int ok = idx / NPAD;             // o * Mpad + k
-        int n = idx % NPAD;
-        diff_lds[ok * NSTRIDE + n] = dsrc[idx] * scale;
+    if constexpr (SPL) {
+        for (int idx = tid; idx < OIMG * NT * 64; idx += 256) {
+            const int l = idx & 63;
+            const int o = (idx >> 6) / NT, ct = (idx >> 6) % NT;
+            const int n = ct * 16 + (l & 15);
+            const int q = l >> 4;
+            uint32_t ph[3], pm[3], pl[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const int g = 3 * q + j;
+                // the same product as the fp32 path stages, then split
+                const float v = g < KS * 4
+                    ? __fmul_rn(dsrc[(o * (KS * 4) + g) * NPAD + n], scale) : 0.0f;
+                const SplitBf16 sp = split_bf16(v);
+                ph[j] = split_bf16_pattern(sp.hi);
+                pm[j] = split_bf16_pattern(sp.mid);
+                pl[j] = split_bf16_pattern(sp.lo);
+            }
+            const SplitBf16 sb = split_bf16(__fmul_rn(base[o * NPAD + n], scale));
+            const uint32_t pb = q == 0 ? split_bf16_pattern(sb.hi)
+                              : q == 1 ? split_bf16_pattern(sb.mid)
+                              : q == 2 ? split_bf16_pattern(sb.lo) : 0u;
+            bw_lds[idx] = (u32x4){ph[0] | (ph[1] << 16), ph[2] | (pm[0] << 16),
+                                  pm[1] | (pm[2] << 16), pb};
+            bn_lds[idx] = (u32x4){pl[0] | (pl[1] << 16), pl[2], 0u, 0u};
+        }
+    } else {
+        for (int idx = tid; idx < OIMG * Mpad * NPAD; idx += 256) {
+            int ok = idx / NPAD;             // o * Mpad + k
+            int n = idx % NPAD;
+            diff_lds[ok * NSTRIDE + n] = dsrc[idx] * scale;
+        }
+        for (int idx = tid; idx < OIMG * NPAD; idx += 256)
+            base_lds[idx] = base[idx] * scale;
     }
-    for (int idx = tid; idx < OIMG * NPAD; idx += 256)
-        base_lds[idx] = base[idx] * scale;
     for (int idx = tid; idx < NPAD; idx += 256) wbg_lds[idx] = wbg[idx];
     __syncthreads();
 
@@ -2473,6 +2535,18 @@ void fused_predict_linear_packed_kernel(  // stay in VGPRs the VALU can read
     const int akcol = lane >> 4;
     const float* dbase = diff_lds + akcol * NSTRIDE + arow;
     const uint64_t* plane = packed + (size_t)b * S;
+
+    bf16x8 bwr[BREG ? NT : 1][OIMG];
+    bf16x8 bnr[BREG ? NT : 1][OIMG];
+    if constexpr (BREG) {
+#pragma unroll
+        for (int ct = 0; ct < NT; ++ct)
+#pragma unroll
+            for (int o = 0; o < OIMG; ++o) {
+                bwr[ct][o] = __builtin_bit_cast(bf16x8, bw_lds[(o * NT + ct) * 64 + lane]);
+                bnr[ct][o] = __builtin_bit_cast(bf16x8, bn_lds[(o * NT + ct) * 64 + lane]);
+            }
+    }
 
     // the word loads are unconditional (row index clamped into the instance)
     // and validity is applied where the word is consumed, one iteration
@@ -2485,7 +2559,8 @@ void fused_predict_linear_packed_kernel(  // stay in VGPRs the VALU can read
         if (ssub0 >= S) break;
         // bit (4*ks) of w is this lane's A element of k-step ks; rows past S
         // carry an all-zero word
-        const uint64_t w = (srow < S ? bits_next : 0ull) >> akcol;
+        const uint64_t wv = srow < S ? bits_next : 0ull;
+        const uint64_t w = wv >> akcol;
         srow += S_SUB;
         bits_next = plane[min(srow, S - 1)];
 
@@ -2505,12 +2580,54 @@ void fused_predict_linear_packed_kernel(  // stay in VGPRs the VALU can read
         for (int ct = 0; ct < NTH; ++ct)
 #pragma unroll
             for (int o = 0; o < OIMG; ++o) {
-                const float b0 =
-                    ct < CTN ? base_lds[o * NPAD + (CT0 + ct) * 16 + arow] : 0.0f;
-                acc[ct][o] = (f32x4){b0, b0, b0, b0};
+                if constexpr (!SPL) {
+                    const float b0 =
+                        ct < CTN ? base_lds[o * NPAD + (CT0 + ct) * 16 + arow] : 0.0f;
+                    acc[ct][o] = (f32x4){b0, b0, b0, b0};
+                }
             }
 
-        if constexpr (KS > 0) {
+        if constexpr (SPL) {
+            // bits 3q..3q+2 of the word are this lane's groups; bf16 1.0 is
+            // 0x3F80; the base slot's A element is 1.0 for every row
+            const uint32_t t = (uint32_t)(wv >> (3 * akcol));
+            const uint32_t e0 = (t & 1u) ? 0x3F80u : 0u;
+            const uint32_t e1 = (t & 2u) ? 0x3F80u : 0u;
+            const uint32_t e2 = (t & 4u) ? 0x3F80u : 0u;
+            const uint32_t e01 = e0 | (e1 << 16);
+            const bf16x8 aw = __builtin_bit_cast(
+                bf16x8, ((u32x4){e01, e2 | (e0 << 16), e1 | (e2 << 16), 0x3F80u}));
+            const bf16x8 an = __builtin_bit_cast(
+                bf16x8, ((u32x4){e01, e2, 0u, 0u}));
+#pragma unroll
+            for (int ct = 0; ct < NTH; ++ct) {
+                if (ct < CTN) {
+#pragma unroll
+                    for (int o = 0; o < OIMG; ++o) {
+                        bf16x8 bw;
+                        if constexpr (BREG) bw = bwr[CT0 + ct][o];
+                        else bw = __builtin_bit_cast(
+                            bf16x8, bw_lds[(o * NT + CT0 + ct) * 64 + lane]);
+                        acc[ct][o] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                            aw, bw, (f32x4){0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
+                    }
+                }
+            }
+#pragma unroll
+            for (int ct = 0; ct < NTH; ++ct) {
+                if (ct < CTN) {
+#pragma unroll
+                    for (int o = 0; o < OIMG; ++o) {
+                        bf16x8 bn;
+                        if constexpr (BREG) bn = bnr[CT0 + ct][o];
+                        else bn = __builtin_bit_cast(
+                            bf16x8, bn_lds[(o * NT + CT0 + ct) * 64 + lane]);
+                        acc[ct][o] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                            an, bn, acc[ct][o], 0, 0, 0);
+                    }
+                }
+            }
+        } else if constexpr (KS > 0) {
             const uint32_t wlo = (uint32_t)w;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
@@ -2640,31 +2757,43 @@ template <int NOUT, int ACT, int NT>
 static int launch_fpp_ks(
     const uint64_t* packed, const float* diff, const float* base,
     const float* wbg, const float* lfnull, float* ey, int B, int S, int Mpad,
-    int link, hipStream_t stream)
+    int link, int mma, hipStream_t stream)
 {
     const int n_stiles = (S + S_TILE - 1) / S_TILE;
     dim3 grid(B * n_stiles), block(256);
     constexpr int NPAD = NT * 16;
     constexpr int NSTRIDE = NPAD + ((16 - (NPAD & 31)) & 31);
     constexpr int OIMG = (ACT == 3) ? 1 : NOUT;
-    const size_t lds = (size_t)(OIMG * Mpad * NSTRIDE + OIMG * NPAD + NPAD) * 4;
+    size_t lds = (size_t)(OIMG * Mpad * NSTRIDE + OIMG * NPAD + NPAD) * 4;
     if (lds > 64 * 1024) return -1;
-#define KSHAP_FPP(KSV) \
-    fused_predict_linear_packed_kernel<NOUT, ACT, NT, KSV> \
+#define KSHAP_FPP(KSV, MMAV) \
+    fused_predict_linear_packed_kernel<NOUT, ACT, NT, KSV, MMAV> \
         <<<grid, block, lds, stream>>>(packed, diff, base, wbg, lfnull, ey, \
                                        B, S, Mpad, link)
     // compile-time k-steps for the sigmoid-type activations (the shapes the
     // step time is spent in); everything else takes the runtime loop
     if constexpr (ACT == 1 || ACT == 3) {
+        // split-operand bf16 path (mma 1 or auto) where 2*Mpad + 3 <= 32 and
+        // the fragments fit the LDS (all shapes but four images x 8 tiles)
+        const size_t lds_split = (size_t)OIMG * NT * 64 * 32 + (size_t)NPAD * 4;
+        if (mma != 0 && Mpad <= 12 && lds_split <= 64 * 1024) {
+            lds = lds_split;
+            switch (Mpad / 4) {
+                case 1: KSHAP_FPP(1, 1); return 0;
+                case 2: KSHAP_FPP(2, 1); return 0;
+                case 3: KSHAP_FPP(3, 1); return 0;
+                default: break;
+            }
+        }
         switch (Mpad / 4) {
-            case 1: KSHAP_FPP(1); return 0;
-            case 2: KSHAP_FPP(2); return 0;
-            case 3: KSHAP_FPP(3); return 0;
-            case 4: KSHAP_FPP(4); return 0;
+            case 1: KSHAP_FPP(1, 0); return 0;
+            case 2: KSHAP_FPP(2, 0); return 0;
+            case 3: KSHAP_FPP(3, 0); return 0;
+            case 4: KSHAP_FPP(4, 0); return 0;
             default: break;
         }
     }
-    KSHAP_FPP(0);
+    KSHAP_FPP(0, 0);
 #undef KSHAP_FPP
     return 0;
 }
@@ -2673,12 +2802,12 @@ template <int NOUT, int ACT>
 static int launch_fpp_nt(
     const uint64_t* packed, const float* diff, const float* base,
     const float* wbg, const float* lfnull, float* ey, int B, int S, int Mpad,
-    int Npad, int link, hipStream_t stream)
+    int Npad, int link, int mma, hipStream_t stream)
 {
 #define KSHAP_FPP_NT(NTV) \
     case NTV: \
         return launch_fpp_ks<NOUT, ACT, NTV>(packed, diff, base, wbg, lfnull, \
-                                             ey, B, S, Mpad, link, stream);
+                                             ey, B, S, Mpad, link, mma, stream);
     switch (Npad / 16) {
         KSHAP_FPP_NT(1) KSHAP_FPP_NT(2) KSHAP_FPP_NT(3) KSHAP_FPP_NT(4)
         KSHAP_FPP_NT(5) KSHAP_FPP_NT(6) KSHAP_FPP_NT(7) KSHAP_FPP_NT(8)
@@ -2691,18 +2820,18 @@ template <int NOUT>
 static int launch_fpp_act(
     const uint64_t* packed, const float* diff, const float* base,
     const float* wbg, const float* lfnull, float* ey, int B, int S, int Mpad,
-    int Npad, int act, int link, hipStream_t stream)
+    int Npad, int act, int link, int mma, hipStream_t stream)
 {
     switch (act) {
         case 0:
-            return launch_fpp_nt<NOUT, 0>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, link, stream);
+            return launch_fpp_nt<NOUT, 0>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, link, mma, stream);
         case 1:
-            return launch_fpp_nt<NOUT, 1>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, link, stream);
+            return launch_fpp_nt<NOUT, 1>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, link, mma, stream);
         case 2:
-            return launch_fpp_nt<NOUT, 2>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, link, stream);
+            return launch_fpp_nt<NOUT, 2>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, link, mma, stream);
         case 3:
             if constexpr (NOUT == 2)
-                return launch_fpp_nt<NOUT, 3>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, link, stream);
+                return launch_fpp_nt<NOUT, 3>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, link, mma, stream);
             return -1;
         default:
             return -1;
@@ -2712,17 +2841,19 @@ static int launch_fpp_act(
 extern "C" int launch_fused_predict_linear_packed(
     const uint64_t* packed, const float* diff, const float* base,
     const float* wbg, const float* lfnull, float* ey, int B, int S, int Mpad,
-    int Npad, int n_out, int act, int link, hipStream_t stream)
+    int Npad, int n_out, int act, int link, hipStream_t stream, int mma)
 {
+    // mma: 0 = fp32 MFMA, 1 = split-operand bf16 MFMA, -1 = auto (split where
+    // eligible); an ineligible shape takes the fp32 MFMA path either way
     if (Mpad < 4 || Mpad > MAX_MPAD || Mpad % 4 != 0 || Npad % 16 != 0
-            || Npad < 16 || Npad / 16 > 8)
+            || Npad < 16 || Npad / 16 > 8 || mma < -1 || mma > 1)
         return -1;
     if (link != 0 && (link != 1 || lfnull == nullptr)) return -1;
     if (B <= 0 || S <= 0) return 0;
     switch (n_out) {
-        case 1: return launch_fpp_act<1>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, act, link, stream);
-        case 2: return launch_fpp_act<2>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, act, link, stream);
-        case 4: return launch_fpp_act<4>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, act, link, stream);
+        case 1: return launch_fpp_act<1>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, act, link, mma, stream);
+        case 2: return launch_fpp_act<2>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, act, link, mma, stream);
+        case 4: return launch_fpp_act<4>(packed, diff, base, wbg, lfnull, ey, B, S, Mpad, Npad, act, link, mma, stream);
         default: return -1;
     }
 }
