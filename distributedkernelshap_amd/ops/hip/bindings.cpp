@@ -487,7 +487,7 @@ void fused_predict_tiled(
         partial.data_ptr<float>(), ey.data_ptr<float>(), B, S, M, Mpad,
         Npad, n_out, (int)act, current_stream());
     TORCH_CHECK(rc == 0, "fused_predict_tiled: unsupported shape "
-                         "(Mpad%4==0, Npad%16==0, n_out in {1,2,4})");
+                         "(Mpad%16==0, Npad%16==0, n_out in {1,2,4})");
 }
 
 void build_diff_bf16_tiled(torch::Tensor xp, torch::Tensor bgp,
