@@ -17,8 +17,19 @@ also prints ``max_phi_err_vs_fp64`` (the first ``--selfcheck`` instances
 re-explained in the fp64 device mode on identical coalition masks); both GPU
 paths print a per-stage trace.
 
+``--classes K`` (K >= 3) runs a ``MulticlassSVCPredictor.random`` machine
+instead (kinds ``svm_multiclass`` / ``svm_multiclass_fused``) with
+``--activation`` ``coupling`` (default), ``ovr`` or ``none``, so the cost of
+the one-vs-one epilogue can be read against the same machine without it.
+``none`` fuses for K <= 4 only (P <= 8 pair rows); the main loop does not
+depend on the output count, so for larger K the plain machine with the same
+``--n-sv`` is the epilogue-free baseline. ``--n-out`` sets the plain
+machine's output count. The link is ``logit`` for probabilities and
+``identity`` for ``ovr`` / ``none``.
+
     python benchmarks/km_fused.py                 # all three paths
     python benchmarks/km_fused.py --path fused
+    python benchmarks/km_fused.py --classes 6 --n-sv 256
 """
 from __future__ import annotations
 
@@ -58,11 +69,24 @@ def run_path(args) -> dict:
         n_features=64, n_instances=args.instances,
         n_background=args.background, seed=1000,
     )
-    pred = make_predictor(kind, 64, 2, seed=0, n_sv=args.n_sv,
-                          kernel=args.kernel, degree=args.degree,
-                          coef0=args.coef0)
+    link = "logit"
+    if args.classes:
+        kind = kind.replace("svm", "svm_multiclass")
+        activation = args.activation or "coupling"
+        pred = make_predictor(kind, 64, args.classes, seed=0, n_sv=args.n_sv,
+                              kernel=args.kernel, degree=args.degree,
+                              coef0=args.coef0, activation=activation)
+        if activation != "coupling":
+            link = "identity"
+    else:
+        activation = args.activation or "softmax"
+        pred = make_predictor(kind, 64, args.n_out, seed=0, n_sv=args.n_sv,
+                              kernel=args.kernel, degree=args.degree,
+                              coef0=args.coef0, activation=activation)
+        if activation == "none":
+            link = "identity"
     engine = KernelShapEngine(
-        pred, data.background, groups=data.groups, link="logit", seed=0,
+        pred, data.background, groups=data.groups, link=link, seed=0,
         device=device,
     )
     X_np = data.X[:instances]
@@ -88,6 +112,8 @@ def run_path(args) -> dict:
         "instances": instances,
         "n_sv": args.n_sv,
         "kernel": args.kernel,
+        "classes": args.classes,
+        "activation": activation,
         "steps": steps,
         "warmup": warmup,
         "expl_per_s_median": instances / med,
@@ -99,11 +125,11 @@ def run_path(args) -> dict:
     if device == "cpu":
         return res
     res["km_fused"] = bool(getattr(engine._gpu, "km_fused", False))
-    if kind == "svm_fused":
+    if kind.endswith("_fused"):
         assert res["km_fused"], "fused path expected but not taken"
         k = min(args.selfcheck, instances)
         eng64 = KernelShapEngine(
-            pred, data.background, groups=data.groups, link="logit", seed=0,
+            pred, data.background, groups=data.groups, link=link, seed=0,
             device="cuda", kernels=KernelConfig(predict_dtype="fp64"),
         )
         sv64 = eng64.shap_values(data.X[:k], l1_reg=False)
@@ -132,6 +158,15 @@ def main() -> None:
     ap.add_argument("--kernel", choices=["rbf", "poly"], default="rbf")
     ap.add_argument("--degree", type=int, default=3)
     ap.add_argument("--coef0", type=float, default=0.0)
+    ap.add_argument("--classes", type=int, default=0,
+                    help="K >= 3: a MulticlassSVCPredictor.random machine "
+                         "(default 0: the plain kernel machine)")
+    ap.add_argument("--activation", default=None,
+                    help="coupling | ovr | none with --classes (default "
+                         "coupling); softmax | sigmoid | none without "
+                         "(default softmax)")
+    ap.add_argument("--n-out", type=int, default=2,
+                    help="outputs of the plain machine (ignored with --classes)")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--selfcheck", type=int, default=8,
@@ -143,6 +178,8 @@ def main() -> None:
     args = ap.parse_args()
     if args.steps < 5:
         ap.error("--steps must be at least 5 (median and spread)")
+    if args.classes and args.classes < 3:
+        ap.error("--classes must be 0 or at least 3")
 
     if args.path is not None:
         print(json.dumps(run_path(args)), flush=True)
@@ -155,7 +192,10 @@ def main() -> None:
         "--steps", str(args.steps), "--warmup", str(args.warmup),
         "--selfcheck", str(args.selfcheck),
         "--cpu-instances", str(args.cpu_instances),
+        "--classes", str(args.classes), "--n-out", str(args.n_out),
     ]
+    if args.activation is not None:
+        passthrough += ["--activation", args.activation]
     for name in ("module", "fused", "cpu"):
         cmd = [sys.executable, os.path.abspath(__file__), "--path", name]
         try:

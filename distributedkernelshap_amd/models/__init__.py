@@ -2,6 +2,7 @@ from .predictors import (  # noqa: F401
     KernelMachinePredictor,
     LinearPredictor,
     MLPPredictor,
+    MulticlassSVCPredictor,
     RoutedTreeEnsemblePredictor,
     TorchPredictor,
     TreeEnsemblePredictor,

@@ -24,6 +24,9 @@ Here predictors are first-class objects:
   kernel-machine HIP kernel (squared distance / dot product folded over
   coalition groups, support vectors streamed in tiles, kernel evaluation and
   the contraction with the dual coefficients on chip).
+* ``MulticlassSVCPredictor`` — multi-class one-vs-one ``SVC`` / ``NuSVC``:
+  the same kernel with the pair decisions turned into one-vs-rest scores or
+  coupled probabilities in a per-row epilogue.
 * ``TorchPredictor`` — wraps any torch ``nn.Module`` (MLP / ResNet configs);
   the GPU engine materialises synth tiles on-device and calls the module
   stream-ordered.
@@ -35,7 +38,8 @@ from typing import Optional
 import numpy as np
 
 __all__ = ["KernelMachinePredictor", "LinearPredictor", "MLPPredictor",
-           "RoutedTreeEnsemblePredictor", "TorchPredictor",
+           "MulticlassSVCPredictor", "RoutedTreeEnsemblePredictor",
+           "TorchPredictor",
            "TreeEnsemblePredictor", "make_predictor"]
 
 
@@ -1040,7 +1044,8 @@ class KernelMachinePredictor:
         X = np.asarray(X, dtype=np.float64)
         if X.ndim != 2 or X.shape[1] != self.n_features:
             raise ValueError(f"X must be (n, {self.n_features})")
-        out = np.empty((X.shape[0], self.n_out))
+        # alpha's rows, not n_out: a subclass may reduce them in its activation
+        out = np.empty((X.shape[0], self.alpha.shape[0]))
         # the rbf difference tensor is (rows, V, D): bound it, not (rows, V)
         step = max(1, (1 << 22) // (self.n_sv * self.n_features))
         for lo in range(0, X.shape[0], step):
@@ -1162,8 +1167,9 @@ class KernelMachinePredictor:
             if name in ("SVC", "NuSVC") and len(est.classes_) != 2:
                 raise TypeError(
                     f"multi-class {name} ({len(est.classes_)} classes) is not "
-                    "supported: one-vs-one votes / pairwise coupling are not "
-                    "of the form alpha · k(x, sv)")
+                    "supported here: use MulticlassSVCPredictor.from_sklearn "
+                    "(one-vs-one pair decisions with an ovr / coupling "
+                    "epilogue)")
             sv = dense(est.support_vectors_)
             alpha = dense(est.dual_coef_).reshape(1, -1)
             intercept = np.asarray(est.intercept_, dtype=np.float64).reshape(1)
@@ -1217,6 +1223,285 @@ class KernelMachinePredictor:
         return proba
 
 
+def _pair_index(n_classes: int):
+    """libsvm pair order (0,1), (0,2), …, (K−2, K−1) as two index arrays."""
+    i, j = np.triu_indices(n_classes, 1)
+    return i.astype(np.int64), j.astype(np.int64)
+
+
+class MulticlassSVCPredictor(KernelMachinePredictor):
+    """Multi-class one-vs-one SVM (libsvm ``SVC`` / ``NuSVC``, K ≥ 3).
+
+    The P = K(K−1)/2 pair decisions are ``f = intercept + alpha · k(x, sv)``
+    with ``alpha`` ``(P, V)`` and ``intercept`` ``(P,)`` in libsvm pair order
+    (0,1), (0,2), …, (K−2, K−1); row (i, j) is non-zero only on the support
+    vectors of classes i and j. ``raw()`` returns these pair decisions.
+    ``activation`` turns them into the output:
+
+    * ``"none"``: the pair decisions themselves (sklearn's ``ovo`` decision
+      function), ``n_out = P``;
+    * ``"ovr"``: sklearn's ``_ovr_decision_function``: per pair, class j
+      gets the vote if ``f < 0`` else class i; ``conf_i += f``,
+      ``conf_j −= f``; output ``votes + conf / (3 (|conf| + 1))``,
+      ``n_out = K``;
+    * ``"coupling"``: libsvm's pairwise coupling at its fixed point. With
+      ``r_ij = clip(1 / (1 + exp(prob_a[p] f_p + prob_b[p])), 1e-7, 1 − 1e-7)``
+      and ``r_ji = 1 − r_ij``, ``Q_tt = Σ_{j≠t} r_jt²``,
+      ``Q_tj = −r_jt r_tj``, the output minimises ``pᵀQp`` subject to
+      ``Σp = 1`` (the (K+1) × (K+1) KKT system, solved in fp64),
+      ``n_out = K``. libsvm stops its own iteration at eps = 0.005/K, so
+      ``predict_proba`` differs from this by up to about 3e-3.
+
+    ``__call__`` is the fp64 numpy oracle. The GPU engine runs the fused
+    kernel-machine kernel with a one-vs-one epilogue for K ≤ 6 (``"none"``:
+    P ≤ 8, i.e. K ≤ 4) and the torch module otherwise.
+    """
+
+    _OUT = ("none", "ovr", "coupling")
+
+    def __init__(self, support_vectors, alpha, intercept, n_classes: int,
+                 kernel: str = "rbf", gamma: float = 1.0, coef0: float = 0.0,
+                 degree: int = 3, activation: str = "ovr", prob_a=None,
+                 prob_b=None):
+        super().__init__(support_vectors, alpha, intercept, kernel=kernel,
+                         gamma=gamma, coef0=coef0, degree=degree,
+                         activation=activation)
+        if isinstance(n_classes, bool) or int(n_classes) != n_classes \
+                or int(n_classes) < 3:
+            raise ValueError("n_classes must be an integer >= 3")
+        k = int(n_classes)
+        n_pairs = k * (k - 1) // 2
+        if self.alpha.shape[0] != n_pairs:
+            raise ValueError(
+                f"alpha must be (P, V) with P = K(K-1)/2 = {n_pairs} rows")
+        self.n_classes = k
+        if activation == "coupling":
+            if prob_a is None or prob_b is None:
+                raise ValueError(
+                    "activation='coupling' needs prob_a and prob_b")
+            pa = np.asarray(prob_a, dtype=np.float64).reshape(-1)
+            pb = np.asarray(prob_b, dtype=np.float64).reshape(-1)
+            if pa.shape[0] != n_pairs or pb.shape[0] != n_pairs:
+                raise ValueError("prob_a and prob_b must have P entries")
+            if not (np.isfinite(pa).all() and np.isfinite(pb).all()):
+                raise ValueError("prob_a and prob_b must be finite")
+            self.prob_a, self.prob_b = pa, pb
+        else:
+            self.prob_a = self.prob_b = None
+
+    @property
+    def n_raw(self) -> int:
+        return self.alpha.shape[0]
+
+    @property
+    def n_out(self) -> int:
+        return self.n_raw if self.activation == "none" else self.n_classes
+
+    def ovr(self, f: np.ndarray) -> np.ndarray:
+        """sklearn's ``_ovr_decision_function`` of pair decisions ``(n, P)``."""
+        k = self.n_classes
+        votes = np.zeros((f.shape[0], k))
+        conf = np.zeros((f.shape[0], k))
+        for p, (i, j) in enumerate(zip(*_pair_index(k))):
+            neg = f[:, p] < 0
+            votes[:, j] += neg
+            votes[:, i] += ~neg
+            conf[:, i] += f[:, p]
+            conf[:, j] -= f[:, p]
+        return votes + conf / (3.0 * (np.abs(conf) + 1.0))
+
+    def pair_probabilities(self, f: np.ndarray) -> np.ndarray:
+        """``r[n, i, j]`` (diagonal 0) from pair decisions ``(n, P)``."""
+        k = self.n_classes
+        i, j = _pair_index(k)
+        rij = np.clip(1.0 / (1.0 + np.exp(f * self.prob_a + self.prob_b)),
+                      1e-7, 1.0 - 1e-7)
+        r = np.zeros((f.shape[0], k, k))
+        r[:, i, j] = rij
+        r[:, j, i] = 1.0 - rij
+        return r
+
+    def coupling(self, f: np.ndarray) -> np.ndarray:
+        """The minimiser of ``pᵀQp`` subject to ``Σp = 1`` (fp64 KKT solve)."""
+        k = self.n_classes
+        r = self.pair_probabilities(f)
+        q = -r.transpose(0, 2, 1) * r                 # Q_tj = -r_jt r_tj
+        idx = np.arange(k)
+        q[:, idx, idx] = (r * r).sum(axis=1)          # Q_tt = sum_j r_jt^2
+        kkt = np.zeros((f.shape[0], k + 1, k + 1))
+        kkt[:, :k, :k] = q
+        kkt[:, :k, k] = 1.0
+        kkt[:, k, :k] = 1.0
+        rhs = np.zeros((f.shape[0], k + 1, 1))
+        rhs[:, k, 0] = 1.0
+        return np.linalg.solve(kkt, rhs)[:, :k, 0]
+
+    def __call__(self, X: np.ndarray) -> np.ndarray:
+        f = self.raw(X)
+        if self.activation == "ovr":
+            return self.ovr(f)
+        if self.activation == "coupling":
+            return self.coupling(f)
+        return f
+
+    def kernel_machine_params(self):
+        params = super().kernel_machine_params()
+        params.update(n_classes=self.n_classes, prob_a=self.prob_a,
+                      prob_b=self.prob_b)
+        return params
+
+    def build_module(self, dtype=None):
+        import torch
+
+        from .km_module import KernelMachineModule
+
+        dtype = dtype or torch.float32
+        return KernelMachineModule(
+            self.support_vectors, self.alpha, self.intercept, self.kernel,
+            self.gamma, self.coef0, self.degree, self.activation, dtype,
+            n_classes=self.n_classes, prob_a=self.prob_a,
+            prob_b=self.prob_b).eval()
+
+    # ------------------------------------------------------------------ #
+
+    @classmethod
+    def random(cls, d: int, n_classes: int = 3, n_sv: int = 256,
+               kernel: str = "rbf", seed: int = 0, activation: str = "ovr",
+               coef0: float = 0.0, degree: int = 3):
+        """Philox-seeded machine with the libsvm structure: standard-normal
+        support vectors in contiguous class blocks, ``gamma = 1/d``, pair row
+        (i, j) non-zero only on the blocks of classes i and j and scaled so
+        that ``Σ_v |alpha[p, v]| = 4``; ``prob_a`` in (−2, −0.5), ``prob_b``
+        within ±0.1 (always drawn, used by ``"coupling"``)."""
+        k = int(n_classes)
+        if k < 3:
+            raise ValueError("n_classes must be an integer >= 3")
+        if n_sv < k:
+            raise ValueError("n_sv must be at least n_classes")
+        rng = np.random.Generator(np.random.Philox(key=[seed, 0x0501]))
+        sv = rng.normal(size=(n_sv, d))
+        cuts = np.linspace(0, n_sv, k + 1).round().astype(int)
+        pi, pj = _pair_index(k)
+        alpha = np.zeros((pi.shape[0], n_sv))
+        dense = rng.normal(size=alpha.shape)
+        for p, (i, j) in enumerate(zip(pi, pj)):
+            for c in (i, j):
+                alpha[p, cuts[c] : cuts[c + 1]] = dense[p, cuts[c] : cuts[c + 1]]
+        alpha *= 4.0 / np.abs(alpha).sum(axis=1, keepdims=True)
+        intercept = rng.normal(0.0, 0.1, size=pi.shape[0])
+        prob_a = -rng.uniform(0.5, 2.0, size=pi.shape[0])
+        prob_b = rng.uniform(-0.1, 0.1, size=pi.shape[0])
+        return cls(sv, alpha, intercept, k, kernel=kernel, gamma=1.0 / d,
+                   coef0=coef0, degree=degree, activation=activation,
+                   prob_a=prob_a, prob_b=prob_b)
+
+    @classmethod
+    def from_sklearn(cls, est, output: str = "decision"):
+        """Wrap a fitted multi-class ``SVC`` / ``NuSVC`` with an rbf or
+        polynomial kernel. ``output`` is ``"ovo"`` (the P pair decisions),
+        ``"ovr"`` (K scores), ``"decision"`` (whichever of the two
+        ``est.decision_function_shape`` names) or ``"proba"`` (K coupled
+        probabilities; needs ``probability=True``). Outputs follow
+        ``est.classes_``. Raises ``TypeError`` with the reason for anything
+        else. ``ovo`` and ``ovr`` are checked against the public
+        ``decision_function`` on a few probe rows (1e-9 relative), ``proba``
+        against ``predict_proba`` at a loose 2e-2: libsvm stops its coupling
+        iteration early (about 3e-3 from the fixed point)."""
+        if output not in ("decision", "ovo", "ovr", "proba"):
+            raise ValueError(
+                f"unknown output {output!r} (decision, ovo, ovr, proba)")
+        name = type(est).__name__
+        if not type(est).__module__.startswith("sklearn."):
+            raise TypeError(f"{name} is not a sklearn estimator")
+        if name not in ("SVC", "NuSVC"):
+            raise TypeError(
+                f"{name} is not a multi-class kernel machine (SVC, NuSVC)")
+        kern = est.kernel
+        if callable(kern):
+            raise TypeError(f"{name} with a callable kernel is not supported")
+        if kern == "linear":
+            raise TypeError(
+                f"{name}(kernel='linear') is a linear model: use "
+                "LinearPredictor with its coef_ / intercept_")
+        if kern in ("poly", "polynomial"):
+            kern = "poly"
+        elif kern != "rbf":
+            raise TypeError(
+                f"{name}(kernel={kern!r}) is not supported (rbf, poly)")
+        k = len(est.classes_)
+        if k < 3:
+            raise TypeError(
+                f"binary {name}: use KernelMachinePredictor.from_sklearn")
+        if output == "proba" and (
+                not getattr(est, "probability", False)
+                or np.size(getattr(est, "probA_", ())) != k * (k - 1) // 2):
+            raise TypeError(
+                f"output='proba' needs an {name} fitted with probability=True")
+        degree = est.degree if kern == "poly" else 3
+        if kern == "poly" and (float(degree) != int(degree) or degree < 1):
+            raise TypeError(
+                f"{name} has degree {degree!r}; only integer degrees >= 1 "
+                "are supported")
+        coef0 = float(est.coef0) if kern == "poly" else 0.0
+        gamma = float(est._gamma if isinstance(est.gamma, str) else est.gamma)
+
+        def dense(a):
+            return np.asarray(a.toarray() if hasattr(a, "toarray") else a,
+                              dtype=np.float64)
+
+        sv = dense(est.support_vectors_)
+        dual = dense(est.dual_coef_)                       # (K-1, V)
+        start = np.concatenate([[0], np.cumsum(est.n_support_)]).astype(int)
+        pi, pj = _pair_index(k)
+        alpha = np.zeros((pi.shape[0], sv.shape[0]))
+        # libsvm: the coefficients of class i's vectors against class j sit
+        # in row j-1 (j > i) resp. row j (j < i) of dual_coef_
+        for p, (i, j) in enumerate(zip(pi, pj)):
+            alpha[p, start[i] : start[i + 1]] = dual[j - 1, start[i] : start[i + 1]]
+            alpha[p, start[j] : start[j + 1]] = dual[i, start[j] : start[j + 1]]
+        intercept = np.asarray(est.intercept_, dtype=np.float64).reshape(-1)
+        if output == "decision":
+            output = est.decision_function_shape
+            if output not in ("ovo", "ovr"):
+                raise TypeError(
+                    f"{name} has decision_function_shape {output!r}")
+        act = {"ovo": "none", "ovr": "ovr", "proba": "coupling"}[output]
+        extra = {}
+        if act == "coupling":
+            extra = dict(prob_a=np.asarray(est.probA_, dtype=np.float64),
+                         prob_b=np.asarray(est.probB_, dtype=np.float64))
+        try:
+            pred = cls(sv, alpha, intercept, k, kernel=kern, gamma=gamma,
+                       coef0=coef0, degree=int(degree), activation=act, **extra)
+        except ValueError as e:
+            raise TypeError(f"{name} cannot be wrapped: {e}") from None
+        rng = np.random.Generator(np.random.Philox(key=[0, 0x5EED]))
+        pick = rng.integers(sv.shape[0], size=4)
+        spread = sv.std(axis=0) + 1e-12
+        probes = sv[pick] + 0.5 * spread * rng.normal(size=(4, sv.shape[1]))
+        if act == "coupling":
+            lib = np.asarray(est.predict_proba(probes), dtype=np.float64)
+            if np.abs(pred(probes) - lib).max() > 2e-2:
+                raise TypeError(
+                    f"{name}: the coupled pair probabilities do not "
+                    "reproduce predict_proba")
+            return pred
+        # a shallow copy shares the fitted arrays; the caller's estimator
+        # keeps its decision_function_shape
+        import copy
+
+        view = copy.copy(est)
+        view.decision_function_shape = output
+        sc = np.asarray(view.decision_function(probes), dtype=np.float64)
+        own = pred(probes)
+        if own.shape != sc.shape or \
+                np.abs(own - sc).max() > 1e-9 * (1.0 + np.abs(sc).max()):
+            raise TypeError(
+                f"{name}: the parameters read from the estimator do not "
+                "reproduce its decision_function")
+        return pred
+
+
 def make_predictor(kind: str, d: int, n_out: int = 2, seed: int = 0, **kw):
     """Registry entry point used by benchmarks and serve config."""
     if kind == "linear":
@@ -1231,6 +1516,16 @@ def make_predictor(kind: str, d: int, n_out: int = 2, seed: int = 0, **kw):
             return pred
         # the same seeded machine behind the generic module path, so the
         # two predict paths are directly comparable
+        return TorchPredictor(pred.build_module(), device=kw.get("device"))
+    if kind in ("svm_multiclass", "svm_multiclass_fused"):
+        # n_out is the class count here
+        pred = MulticlassSVCPredictor.random(
+            d, n_out, n_sv=kw.get("n_sv", 256), kernel=kw.get("kernel", "rbf"),
+            seed=seed, activation=kw.get("activation", "coupling"),
+            coef0=kw.get("coef0", 0.0), degree=kw.get("degree", 3),
+        )
+        if kind == "svm_multiclass_fused":
+            return pred
         return TorchPredictor(pred.build_module(), device=kw.get("device"))
     if kind in ("trees", "trees_fused"):
         pred = TreeEnsemblePredictor.random(

@@ -496,7 +496,10 @@ class GpuKernelShap:
 
     # ------------------------------------------------------------------ #
     # KernelMachinePredictor: fused_predict_kernelmachine (K4k) with the
-    # GEMM-form torch module as the out-of-envelope fallback
+    # GEMM-form torch module as the out-of-envelope fallback.
+    # MulticlassSVCPredictor comes through the same hook: its "ovr" and
+    # "coupling" activations launch fused_predict_kernelmachine_pairs (K4kp)
+    # from km_pack.fused_predict, and ey has n_out = K columns
 
     def _init_kernel_machine(self, predictor):
         from . import km_pack

@@ -124,6 +124,13 @@ extern "C" int launch_fused_predict_trees_walk(
     const unsigned* cat_left, int C, hipStream_t stream);
 
 // km_kernels.hip
+extern "C" int launch_fused_predict_kernelmachine_pairs(
+    const uint8_t* masks, const float* xp, const float* bgpn,
+    const float* base, const float* alpha, const float* icpt,
+    const float* prob_a, const float* prob_b, const float* wbg, float* ey,
+    int B, int S, int M, int Mpad, int N, int Vpad, int n_classes,
+    int n_pairs, int act, int kernel, float gamma, float coef0, int degree,
+    hipStream_t stream);
 extern "C" int launch_fused_predict_kernelmachine(
     const uint8_t* masks, const float* xp, const float* bgpn,
     const float* base, const float* alpha, const float* icpt,
@@ -779,9 +786,74 @@ void fused_predict_kernelmachine(
     TORCH_CHECK(rc == 0, envelope);
 }
 
+void fused_predict_kernelmachine_pairs(
+    torch::Tensor masks, torch::Tensor xp, torch::Tensor bgpn,
+    torch::Tensor base, torch::Tensor alpha, torch::Tensor intercept,
+    torch::Tensor prob_a, torch::Tensor prob_b, torch::Tensor wbg,
+    torch::Tensor ey, int64_t kernel, double gamma, double coef0,
+    int64_t degree, int64_t act, int64_t n_classes, int64_t n_pairs) {
+    static const char* envelope =
+        "fused_predict_kernelmachine_pairs: outside the supported envelope "
+        "(rbf or poly of degree 1-8, at most 2048 support vectors after "
+        "padding to 16, 3 to 6 classes with K(K-1)/2 pair rows, act 3 (ovr) "
+        "or 4 (coupling), M <= Mpad <= 64 with Mpad a multiple of 16)";
+    CHECK_DEV(masks); CHECK_DEV(xp); CHECK_DEV(bgpn); CHECK_DEV(base);
+    CHECK_DEV(alpha); CHECK_DEV(intercept); CHECK_DEV(prob_a);
+    CHECK_DEV(prob_b); CHECK_DEV(wbg); CHECK_DEV(ey);
+    TORCH_CHECK(masks.dtype() == torch::kUInt8 && masks.dim() == 3,
+                "masks must be u8 (B,S,M)");
+    TORCH_CHECK(xp.dtype() == torch::kFloat32 && xp.dim() == 3,
+                "xp must be f32 (B,Vpad,Mpad)");
+    const int B = masks.size(0), S = masks.size(1), M = masks.size(2);
+    const int Vpad = xp.size(1), Mpad = xp.size(2);
+    TORCH_CHECK(xp.size(0) == B, "xp must be f32 (B,Vpad,Mpad)");
+    TORCH_CHECK(bgpn.dtype() == torch::kFloat32 && bgpn.dim() == 3
+                && bgpn.size(1) == Vpad && bgpn.size(2) == Mpad,
+                "bgpn must be f32 (N,Vpad,Mpad)");
+    const int N = bgpn.size(0);
+    TORCH_CHECK(base.dtype() == torch::kFloat32 && base.dim() == 2
+                && base.size(0) == N && base.size(1) == Vpad,
+                "base must be f32 (N,Vpad)");
+    TORCH_CHECK(alpha.dtype() == torch::kFloat32 && alpha.dim() == 2
+                && alpha.size(0) == 16 && alpha.size(1) == Vpad,
+                "alpha must be f32 (16,Vpad)");
+    TORCH_CHECK(intercept.dtype() == torch::kFloat32 && intercept.numel() == 16,
+                "intercept must be f32 (16)");
+    TORCH_CHECK(prob_a.dtype() == torch::kFloat32 && prob_a.numel() == 16
+                && prob_b.dtype() == torch::kFloat32 && prob_b.numel() == 16,
+                "prob_a and prob_b must be f32 (16)");
+    TORCH_CHECK(wbg.dtype() == torch::kFloat32 && wbg.numel() == N,
+                "wbg must be f32 (N)");
+    TORCH_CHECK(ey.dtype() == torch::kFloat32 && ey.dim() == 3
+                && ey.size(0) == B && ey.size(1) == S
+                && ey.size(2) == n_classes,
+                "ey must be f32 (B,S,n_classes)");
+    TORCH_CHECK(n_classes >= 0 && n_classes < (1 << 16) && n_pairs >= 0
+                && n_pairs < (1 << 30), envelope);
+    int rc = launch_fused_predict_kernelmachine_pairs(
+        masks.data_ptr<uint8_t>(), xp.data_ptr<float>(), bgpn.data_ptr<float>(),
+        base.data_ptr<float>(), alpha.data_ptr<float>(),
+        intercept.data_ptr<float>(), prob_a.data_ptr<float>(),
+        prob_b.data_ptr<float>(), wbg.data_ptr<float>(), ey.data_ptr<float>(),
+        B, S, M, Mpad, N, Vpad, (int)n_classes, (int)n_pairs, (int)act,
+        (int)kernel, (float)gamma, (float)coef0, (int)degree, current_stream());
+    TORCH_CHECK(rc == 0, envelope);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+    m.def("fused_predict_kernelmachine_pairs", &fused_predict_kernelmachine_pairs,
+          "fused one-vs-one kernel-machine predict (K4kp): the K4k main loop "
+          "over K(K-1)/2 pair rows with a per-row epilogue (ovr votes or "
+          "pairwise coupling) into K class scores",
+          pybind11::arg("masks"), pybind11::arg("xp"), pybind11::arg("bgpn"),
+          pybind11::arg("base"), pybind11::arg("alpha"),
+          pybind11::arg("intercept"), pybind11::arg("prob_a"),
+          pybind11::arg("prob_b"), pybind11::arg("wbg"), pybind11::arg("ey"),
+          pybind11::arg("kernel"), pybind11::arg("gamma"),
+          pybind11::arg("coef0"), pybind11::arg("degree"), pybind11::arg("act"),
+          pybind11::arg("n_classes"), pybind11::arg("n_pairs"));
     m.def("fused_predict_kernelmachine", &fused_predict_kernelmachine,
           "fused kernel-machine predict (K4k): distance / dot product folded "
           "over varying groups, support vectors streamed in tiles of 16, "

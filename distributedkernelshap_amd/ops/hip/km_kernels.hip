@@ -45,6 +45,27 @@
 // KM_NB = 4 rows in flight: 64 accumulator registers for z next to 16 for the
 // x term and 16 for the running tile; the x term then costs 16 of every 96
 // MFMAs at Mpad = 64.
+//
+//   K4kp fused_predict_kernelmachine_pairs — the same kernel (EPI = 1) for a
+//       one-vs-one multi-class SVM with K <= 6 classes: the output rows of z
+//       are the P = K(K-1)/2 <= 15 pair decisions in libsvm order, and a
+//       per-row epilogue turns them into K class scores before the weighted
+//       background reduction:
+//           act 3 (ovr)       votes + conf / (3 (|conf| + 1))
+//           act 4 (coupling)  argmin p'Qp, sum p = 1, with Q built from the
+//                             Platt pair probabilities
+// The pair decisions of one sample sit in all four lane quarters (row =
+// 4 (lane>>4) + reg), so a wave stages the 16 x 64 tile of one background row
+// in its own quarter of ``red`` and reads it back with lane = sample (column
+// reads at stride 64: conflict-free).  Store and load are ordered within the
+// wave only — the waves own different numbers of rows, so there is no
+// workgroup barrier inside the row loop.  Rows >= P (alpha = 0) are never
+// read back.  Coupling solves the (K+1) x (K+1) KKT system
+// [[Q, 1], [1', 0]] [p; lambda] = [0; 1] by LU with partial pivoting in
+// registers: every index is a compile-time constant, the pivot is brought up
+// by compare-and-swap of whole rows, and the trip counts depend on K alone
+// (wave-uniform).  The K scores accumulate per lane; the cross-wave sum stays
+// in wave order, so two launches are bit-identical here too.
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -59,6 +80,7 @@ typedef __attribute__((ext_vector_type(4))) float km_f32x4;
 #define KM_MAX_NOUT 8
 #define KM_MAX_M 64        // varying groups
 #define KM_MAX_DEGREE 8
+#define KM_MAX_CLS 6       // classes of the one-vs-one epilogue (15 pair rows)
 
 struct KmArgs {
     const uint8_t* masks;   // (B, S, M) raw coalition masks
@@ -71,6 +93,10 @@ struct KmArgs {
     float* ey;              // (B, S, n_out)
     int B, S, M, N, Vpad, n_out, act, degree;
     float gamma, coef0;
+    // one-vs-one epilogue (EPI = 1) only
+    const float* prob_a;    // (16) Platt slope per pair
+    const float* prob_b;    // (16) Platt offset per pair
+    int K;                  // classes; n_out = K
 };
 
 template <int KCH>
@@ -108,7 +134,7 @@ __device__ __forceinline__ void km_gemm(
 
 // Two workgroups per CU (two waves per SIMD): the compiler is held to 256
 // registers, which it meets without scratch (252-254 at Mpad = 64).
-template <int KCH, bool POLY>
+template <int KCH, bool POLY, int EPI>
 __global__ __launch_bounds__(KM_NW * 64, 2)
 void fused_predict_km_kernel(KmArgs p)
 {
@@ -159,6 +185,11 @@ void fused_predict_km_kernel(KmArgs p)
     km_f32x4 eyacc[4];
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) eyacc[ct] = (km_f32x4){0, 0, 0, 0};
+    // EPI = 1: the K class scores of sample ``lane``, summed over this
+    // wave's rows (exact zeros for a wave without rows)
+    float eyk[KM_MAX_CLS];
+#pragma unroll
+    for (int k = 0; k < KM_MAX_CLS; ++k) eyk[k] = 0.0f;
 
     km_f32x4 a_cur[KCH], a_nxt[KCH];
     if (nlo < nhi) km_load<KCH>(xpl, a_cur);
@@ -236,48 +267,200 @@ void fused_predict_km_kernel(KmArgs p)
             for (int kc = 0; kc < KCH; ++kc) a_cur[kc] = a_nxt[kc];
         }
 
-        // activation over the outputs (registers r and lane quarters), then
-        // the weighted background reduction, in row order
+        if constexpr (EPI == 1) {
+            // one-vs-one epilogue, one background row at a time
+            float* stage = red + wave * (16 * 64);
+            const int K = p.K;
+#pragma nounroll
+            for (int nb = 0; nb < cnt; ++nb) {
+                km_f32x4 zz[4];
 #pragma unroll
-        for (int nb = 0; nb < KM_NB; ++nb) {
-            if (nb < cnt) {
+                for (int ct = 0; ct < 4; ++ct) zz[ct] = z[0][ct];
+#pragma unroll
+                for (int q = 1; q < KM_NB; ++q)
+                    if (nb == q) {                    // wave-uniform
+#pragma unroll
+                        for (int ct = 0; ct < 4; ++ct) zz[ct] = z[q][ct];
+                    }
                 const float wn = p.wbg[n0 + nb];
 #pragma unroll
-                for (int ct = 0; ct < 4; ++ct) {
-                    float zb[4], pr[4];
+                for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) zb[r] = z[nb][ct][r] + icv[r];
-                    if (p.act == 2) {
-                        float mx = -INFINITY;
+                    for (int r = 0; r < 4; ++r)
+                        stage[(vq + r) * 64 + ct * 16 + arow] = zz[ct][r] + icv[r];
+                // the tile was written by other lanes of this wave
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                const float* fcol = stage + lane;     // f_p = fcol[p * 64]
+                if (p.act == 3) {
+                    float votes[KM_MAX_CLS], conf[KM_MAX_CLS];
 #pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            mx = ovalid[r] ? fmaxf(mx, zb[r]) : mx;
-                        mx = fmaxf(mx, __shfl_xor(mx, 16));
-                        mx = fmaxf(mx, __shfl_xor(mx, 32));
-                        float sum = 0.0f;
+                    for (int k = 0; k < KM_MAX_CLS; ++k) votes[k] = conf[k] = 0.0f;
+                    int pp = 0;
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            pr[r] = ovalid[r] ? __expf(zb[r] - mx) : 0.0f;
-                            sum += pr[r];
+                    for (int i = 0; i < KM_MAX_CLS; ++i)
+#pragma unroll
+                        for (int j = i + 1; j < KM_MAX_CLS; ++j)
+                            if (j < K) {
+                                const float f = fcol[pp * 64];
+                                ++pp;
+                                const bool neg = f < 0.0f;
+                                votes[j] += neg ? 1.0f : 0.0f;
+                                votes[i] += neg ? 0.0f : 1.0f;
+                                conf[i] += f;
+                                conf[j] -= f;
+                            }
+#pragma unroll
+                    for (int k = 0; k < KM_MAX_CLS; ++k)
+                        if (k < K)
+                            eyk[k] += wn * (votes[k] + conf[k]
+                                            / (3.0f * (fabsf(conf[k]) + 1.0f)));
+                } else {
+                    // augmented KKT system; variable k >= K is absent (its
+                    // row and column are skipped everywhere), row / column 6
+                    // is the multiplier, column 7 the right-hand side
+                    constexpr int L = KM_MAX_CLS;
+                    float A[L + 1][L + 2];
+#pragma unroll
+                    for (int r = 0; r <= L; ++r)
+#pragma unroll
+                        for (int c = 0; c <= L + 1; ++c) A[r][c] = 0.0f;
+                    int pp = 0;
+#pragma unroll
+                    for (int i = 0; i < L; ++i)
+#pragma unroll
+                        for (int j = i + 1; j < L; ++j)
+                            if (j < K) {
+                                const float arg =
+                                    fmaf(p.prob_a[pp], fcol[pp * 64], p.prob_b[pp]);
+                                ++pp;
+                                // r_ji is the sigmoid of the negated
+                                // argument, not 1 - r_ij
+                                float rij = __builtin_amdgcn_rcpf(1.0f + __expf(arg));
+                                float rji = __builtin_amdgcn_rcpf(1.0f + __expf(-arg));
+                                rij = fminf(fmaxf(rij, 1e-7f), 1.0f - 1e-7f);
+                                rji = fminf(fmaxf(rji, 1e-7f), 1.0f - 1e-7f);
+                                A[i][i] = fmaf(rji, rji, A[i][i]);
+                                A[j][j] = fmaf(rij, rij, A[j][j]);
+                                A[i][j] = A[j][i] = -rij * rji;
+                            }
+#pragma unroll
+                    for (int k = 0; k < L; ++k)
+                        if (k < K) A[k][L] = A[L][k] = 1.0f;
+                    A[L][L + 1] = 1.0f;
+                    float inv[L + 1];
+#pragma unroll
+                    for (int c = 0; c <= L; ++c) {
+                        inv[c] = 0.0f;
+                        if (c < K || c == L) {
+#pragma unroll
+                            for (int r = c + 1; r <= L; ++r)
+                                if (r < K || r == L) {
+                                    // first maximum wins, as in argmax
+                                    const bool sw = fabsf(A[r][c]) > fabsf(A[c][c]);
+#pragma unroll
+                                    for (int k = c; k <= L + 1; ++k) {
+                                        const float t = A[c][k];
+                                        A[c][k] = sw ? A[r][k] : t;
+                                        A[r][k] = sw ? t : A[r][k];
+                                    }
+                                }
+                            inv[c] = 1.0f / A[c][c];
+#pragma unroll
+                            for (int r = c + 1; r <= L; ++r)
+                                if (r < K || r == L) {
+                                    const float m = A[r][c] * inv[c];
+#pragma unroll
+                                    for (int k = c + 1; k <= L + 1; ++k)
+                                        A[r][k] = fmaf(-m, A[c][k], A[r][k]);
+                                }
                         }
-                        sum += __shfl_xor(sum, 16);
-                        sum += __shfl_xor(sum, 32);
-                        const float inv = __builtin_amdgcn_rcpf(sum);
+                    }
+                    float x[L + 1];
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) pr[r] *= inv;
-                    } else if (p.act == 1) {
+                    for (int c = L; c >= 0; --c) {
+                        x[c] = 0.0f;
+                        if (c < K || c == L) {
+                            float acc = A[c][L + 1];
 #pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            pr[r] = __builtin_amdgcn_rcpf(1.0f + __expf(-zb[r]));
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) pr[r] = zb[r];
+                            for (int k = c + 1; k <= L; ++k)
+                                acc = fmaf(-A[c][k], x[k], acc);
+                            x[c] = acc * inv[c];
+                        }
                     }
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) eyacc[ct][r] += wn * pr[r];
+                    for (int k = 0; k < L; ++k)
+                        if (k < K) eyk[k] = fmaf(wn, x[k], eyk[k]);
+                }
+                // the next row overwrites the tile other lanes just read
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
+        } else {
+            // activation over the outputs (registers r and lane quarters), then
+            // the weighted background reduction, in row order
+#pragma unroll
+            for (int nb = 0; nb < KM_NB; ++nb) {
+                if (nb < cnt) {
+                    const float wn = p.wbg[n0 + nb];
+#pragma unroll
+                    for (int ct = 0; ct < 4; ++ct) {
+                        float zb[4], pr[4];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) zb[r] = z[nb][ct][r] + icv[r];
+                        if (p.act == 2) {
+                            float mx = -INFINITY;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                mx = ovalid[r] ? fmaxf(mx, zb[r]) : mx;
+                            mx = fmaxf(mx, __shfl_xor(mx, 16));
+                            mx = fmaxf(mx, __shfl_xor(mx, 32));
+                            float sum = 0.0f;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                pr[r] = ovalid[r] ? __expf(zb[r] - mx) : 0.0f;
+                                sum += pr[r];
+                            }
+                            sum += __shfl_xor(sum, 16);
+                            sum += __shfl_xor(sum, 32);
+                            const float inv = __builtin_amdgcn_rcpf(sum);
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) pr[r] *= inv;
+                        } else if (p.act == 1) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                pr[r] = __builtin_amdgcn_rcpf(1.0f + __expf(-zb[r]));
+                        } else {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) pr[r] = zb[r];
+                        }
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) eyacc[ct][r] += wn * pr[r];
+                    }
                 }
             }
         }
+    }
+
+    if constexpr (EPI == 1) {
+        // the four waves' class scores, added in wave order
+#pragma unroll
+        for (int k = 0; k < KM_MAX_CLS; ++k)
+            red[wave * (16 * 64) + k * 64 + lane] = eyk[k];
+        __syncthreads();
+        const int K = p.K;
+        for (int idx = tid; idx < KM_ROWS * K; idx += NTHR) {
+            const int smp = idx / K;
+            const int k = idx - smp * K;
+            float sum = 0.0f;
+#pragma unroll
+            for (int w = 0; w < KM_NW; ++w)
+                sum += red[w * (16 * 64) + k * 64 + smp];
+            if (s0 + smp < p.S)
+                p.ey[((size_t)b * p.S + s0 + smp) * K + k] = sum;
+        }
+        return;
     }
 
     // the four waves' sums over their rows, added in wave order
@@ -302,7 +485,7 @@ void fused_predict_km_kernel(KmArgs p)
     }
 }
 
-template <int KCH>
+template <int KCH, int EPI>
 static int launch_km_t(const KmArgs& a, int poly, hipStream_t stream)
 {
     const size_t lds = sizeof(float)
@@ -312,9 +495,9 @@ static int launch_km_t(const KmArgs& a, int poly, hipStream_t stream)
     if (nblk > 0x7fffffffLL) return -1;
     dim3 grid((unsigned)nblk), block(KM_NW * 64);
     if (poly)
-        fused_predict_km_kernel<KCH, true><<<grid, block, lds, stream>>>(a);
+        fused_predict_km_kernel<KCH, true, EPI><<<grid, block, lds, stream>>>(a);
     else
-        fused_predict_km_kernel<KCH, false><<<grid, block, lds, stream>>>(a);
+        fused_predict_km_kernel<KCH, false, EPI><<<grid, block, lds, stream>>>(a);
     return 0;
 }
 
@@ -340,10 +523,45 @@ extern "C" int launch_fused_predict_kernelmachine(
     a.alpha = alpha; a.icpt = icpt; a.wbg = wbg; a.ey = ey;
     a.B = B; a.S = S; a.M = M; a.N = N; a.Vpad = Vpad; a.n_out = n_out;
     a.act = act; a.degree = degree; a.gamma = gamma; a.coef0 = coef0;
+    a.prob_a = nullptr; a.prob_b = nullptr; a.K = 0;
     switch (Mpad / 16) {
-        case 1: return launch_km_t<1>(a, kernel, stream);
-        case 2: return launch_km_t<2>(a, kernel, stream);
-        case 3: return launch_km_t<3>(a, kernel, stream);
-        default: return launch_km_t<4>(a, kernel, stream);
+        case 1: return launch_km_t<1, 0>(a, kernel, stream);
+        case 2: return launch_km_t<2, 0>(a, kernel, stream);
+        case 3: return launch_km_t<3, 0>(a, kernel, stream);
+        default: return launch_km_t<4, 0>(a, kernel, stream);
+    }
+}
+
+// One-vs-one variant: alpha / icpt carry n_pairs = K(K-1)/2 pair rows, ey is
+// (B, S, K).  Returns -1 outside the supported envelope: the limits above
+// with, in place of the n_out rule, 3 <= K <= 6 and act 3 (ovr) or
+// 4 (coupling).
+extern "C" int launch_fused_predict_kernelmachine_pairs(
+    const uint8_t* masks, const float* xp, const float* bgpn,
+    const float* base, const float* alpha, const float* icpt,
+    const float* prob_a, const float* prob_b, const float* wbg, float* ey,
+    int B, int S, int M, int Mpad, int N, int Vpad, int n_classes,
+    int n_pairs, int act, int kernel, float gamma, float coef0, int degree,
+    hipStream_t stream)
+{
+    if (kernel != 0 && kernel != 1) return -1;
+    if (kernel == 1 && (degree < 1 || degree > KM_MAX_DEGREE)) return -1;
+    if (n_classes < 3 || n_classes > KM_MAX_CLS) return -1;
+    if (n_pairs != n_classes * (n_classes - 1) / 2) return -1;
+    if (act != 3 && act != 4) return -1;
+    if (M < 1 || M > Mpad || Mpad > KM_MAX_M || Mpad % 16 != 0) return -1;
+    if (Vpad < 16 || Vpad > KM_MAX_V || Vpad % 16 != 0) return -1;
+    if (B < 1 || S < 1 || N < 1) return -1;
+    KmArgs a;
+    a.masks = masks; a.xp = xp; a.bgpn = bgpn; a.base = base;
+    a.alpha = alpha; a.icpt = icpt; a.wbg = wbg; a.ey = ey;
+    a.B = B; a.S = S; a.M = M; a.N = N; a.Vpad = Vpad; a.n_out = n_classes;
+    a.act = act; a.degree = degree; a.gamma = gamma; a.coef0 = coef0;
+    a.prob_a = prob_a; a.prob_b = prob_b; a.K = n_classes;
+    switch (Mpad / 16) {
+        case 1: return launch_km_t<1, 1>(a, kernel, stream);
+        case 2: return launch_km_t<2, 1>(a, kernel, stream);
+        case 3: return launch_km_t<3, 1>(a, kernel, stream);
+        default: return launch_km_t<4, 1>(a, kernel, stream);
     }
 }

@@ -18,6 +18,7 @@ Layouts (k-contiguous, matching ``ops/hip/km_kernels.hip``):
   bgpn   (N, Vpad, Mpad) f32   the same of the background rows, NEGATED
   base   (N, Vpad) f32         sum of a background row's parts over ALL groups
   alpha  (16, Vpad) f32        dual coefficients; intercept (16) f32
+  prob_a, prob_b (16) f32      Platt parameters per pair (one-vs-one epilogue)
 
 Support vectors are zero-padded to a multiple of 16 and the varying-group
 count to a multiple of 16. A padding support vector has all-zero images and
@@ -32,13 +33,18 @@ MAX_SV = 2048
 MAX_NOUT = 8
 MAX_GROUPS = 64
 MAX_DEGREE = 8
+# one-vs-one epilogue (MulticlassSVCPredictor, "ovr" / "coupling"): the pair
+# decisions are the rows of the 16-row accumulator tile, of which row 15 idles
+MAX_PAIRS = 15
+MAX_CLASSES = 6
 
 # Upper bound for the per-call workspaces of one kernel launch: the xp image
 # and the fp64 intermediates behind it. The engine splits a bucket along B
 # so that a launch stays below it.
 WORKSPACE_BYTES = 256 << 20
 
-ACT_CODE = {"none": 0, "sigmoid": 1, "softmax": 2}
+ACT_CODE = {"none": 0, "sigmoid": 1, "softmax": 2, "ovr": 3, "coupling": 4}
+PAIR_ACTS = ("ovr", "coupling")
 KERNEL_CODE = {"rbf": 0, "poly": 1}
 
 
@@ -55,7 +61,11 @@ def envelope_reason(params: dict):
     n_out, n_sv = np.asarray(params["alpha"]).shape
     if _pad_to(n_sv, 16) > MAX_SV:
         return f"{n_sv} support vectors (supported: <= {MAX_SV})"
-    if n_out > MAX_NOUT:
+    if params["activation"] in PAIR_ACTS:
+        k = int(params["n_classes"])
+        if k > MAX_CLASSES or n_out > MAX_PAIRS:
+            return f"{k} classes (supported: <= {MAX_CLASSES})"
+    elif n_out > MAX_NOUT:
         return f"n_out {n_out} (supported: <= {MAX_NOUT})"
     if params["kernel"] == "poly" and params["degree"] > MAX_DEGREE:
         return f"degree {params['degree']} (supported: <= {MAX_DEGREE})"
@@ -81,7 +91,20 @@ def pack_machine(params: dict, col_group, n_groups: int, device) -> dict:
     cg = t.as_tensor(np.asarray(col_group), dtype=t.int64, device=device)
     onehot = t.zeros(d, n_groups, dtype=t.float64, device=device)
     onehot[t.arange(d, device=device), cg] = 1.0
+    pairs = {}
+    if params["activation"] in PAIR_ACTS:
+        # the epilogue's operands: K and, for coupling, the Platt parameters
+        # (zero-padded; the kernel reads entries below P only)
+        prob = t.zeros(2, 16, dtype=t.float64, device=device)
+        if params["activation"] == "coupling":
+            for r, name in enumerate(("prob_a", "prob_b")):
+                v = np.asarray(params[name], dtype=np.float64).reshape(-1)
+                prob[r, : min(v.shape[0], 16)] = t.as_tensor(v[:16], device=device)
+        pairs = {"n_classes": int(params["n_classes"]),
+                 "prob_a": prob[0].float().contiguous(),
+                 "prob_b": prob[1].float().contiguous()}
     return {
+        **pairs,
         "kernel": params["kernel"], "gamma": float(params["gamma"]),
         "coef0": float(params["coef0"]), "degree": int(params["degree"]),
         "act": params["activation"], "n_out": n_out, "n_sv": n_sv,
@@ -138,7 +161,17 @@ def instances_per_launch(pack: dict, d: int, m: int) -> int:
 
 
 def fused_predict(ext, pack: dict, masks, xp, bgpn, base_img, wbg, ey):
-    """One launch of ``fused_predict_kernelmachine``; returns ``ey``."""
+    """One launch of ``fused_predict_kernelmachine`` (or, for the one-vs-one
+    activations, ``fused_predict_kernelmachine_pairs``); returns ``ey``."""
+    if pack["act"] in PAIR_ACTS:
+        ext.fused_predict_kernelmachine_pairs(
+            masks, xp, bgpn, base_img, pack["alpha"], pack["intercept"],
+            pack["prob_a"], pack["prob_b"], wbg, ey,
+            KERNEL_CODE[pack["kernel"]], pack["gamma"], pack["coef0"],
+            pack["degree"], ACT_CODE[pack["act"]], pack["n_classes"],
+            pack["n_out"],
+        )
+        return ey
     ext.fused_predict_kernelmachine(
         masks, xp, bgpn, base_img, pack["alpha"], pack["intercept"], wbg, ey,
         KERNEL_CODE[pack["kernel"]], pack["gamma"], pack["coef0"],
