@@ -22,6 +22,12 @@ instead, four kernels from the instances to phi_full, with no u8 masks:
   fused_predict_linear_packed (K3p)  -> eyAdj (link fused)
   wls_solve_packed (K7p)             -> phi_full (B,n_groups,n_out)
 
+Which of these a bucket gets is decided by the pure functions of
+``routes.py`` (envelopes, predict route, WLS route); ``GpuKernelShap`` only
+dispatches on their answers. The MLP, tree and kernel-machine families each
+live in one object of ``predict_backends.py`` (``GpuKernelShap.backend``):
+fallback module, fp64 forward, fused launch and workspace estimate.
+
 The reference's equivalent work is the per-instance shap 0.35.0 loop invoked
 from ``explainers/kernel_shap.py:250``: sampling -> synth -> predict_proba ->
 mean -> WLS, one instance at a time on one CPU core. Here the whole
@@ -34,7 +40,8 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import load_extension
+from . import load_extension, routes
+from .predict_backends import KernelMachineBackend, MlpBackend, TreeBackend
 from ..core.sampler import CoalitionPlan
 
 logger = logging.getLogger(__name__)
@@ -94,13 +101,7 @@ class GpuKernelShap:
 
         self.linear = None
         self.module = None
-        self.mlp = None          # fp64 weights + operand images (MLPPredictor)
-        self.mlp_fused = False   # True when fused_predict_mlp serves this engine
-        self.trees = None        # fp64 module + packed tables (TreeEnsemblePredictor)
-        self.trees_fused = False  # True when a fused tree kernel serves this engine
-        self.trees_kernel = None  # "bits" (K4t), "walk" (K4w) or None (module)
-        self.km = None           # fp64 module + operand images (KernelMachinePredictor)
-        self.km_fused = False    # True when fused_predict_kernelmachine serves this engine
+        self.backend = None      # MLP / tree / kernel-machine family object
         lp = getattr(engine.predictor, "linear_params", None)
         if lp is not None:
             W, b, act = lp()
@@ -116,11 +117,11 @@ class GpuKernelShap:
             self.bg_part = bg_part
             self.baseN = self.bg @ self.linear["W"].T + self.linear["b"]  # (N, o)
         elif getattr(engine.predictor, "mlp_params", None) is not None:
-            self._init_mlp(engine.predictor)
+            self.backend = MlpBackend(self, engine.predictor)
         elif getattr(engine.predictor, "tree_params", None) is not None:
-            self._init_trees(engine.predictor)
+            self.backend = TreeBackend(self, engine.predictor)
         elif getattr(engine.predictor, "kernel_machine_params", None) is not None:
-            self._init_kernel_machine(engine.predictor)
+            self.backend = KernelMachineBackend(self, engine.predictor)
         else:
             tm = getattr(engine.predictor, "torch_module", None)
             if tm is not None:
@@ -143,6 +144,8 @@ class GpuKernelShap:
                     "torch_module(); got a plain callable. Wrap it in "
                     "TorchPredictor or use device='cpu'."
                 )
+        if self.backend is not None:
+            self.module = self.backend.module
 
         self.fnull = t.tensor(engine.fnull, dtype=t.float32, device=self.device)
         # varying-group check via column extrema: x differs from ALL
@@ -191,439 +194,36 @@ class GpuKernelShap:
         return buf
 
     # ------------------------------------------------------------------ #
-    # MLPPredictor: fused_predict_mlp (K4m) with the torch module as the
-    # out-of-envelope fallback
+    # which path serves a non-linear family (read-only views of the backend)
 
-    def _init_mlp(self, predictor):
-        import copy
+    @property
+    def mlp_fused(self):
+        return isinstance(self.backend, MlpBackend) and self.backend.fused
 
-        from . import mlp_pack
+    @property
+    def trees_fused(self):
+        return isinstance(self.backend, TreeBackend) and self.backend.fused
 
-        t = self.torch
-        kc = self.engine.kernels
-        if kc.predict_dtype not in ("fp32", "bf16", "fp64"):
-            raise ValueError(
-                f"predict_dtype={kc.predict_dtype!r} is not available for "
-                "MLPPredictor; supported: 'fp32', 'bf16' (fused MLP kernel) "
-                "and 'fp64' (verification)"
-            )
-        W, b, hid, act = predictor.mlp_params()
-        self.mlp = {
-            "W64": [t.tensor(np.asarray(w), dtype=t.float64, device=self.device)
-                    for w in W],
-            "b64": [t.tensor(np.asarray(v), dtype=t.float64, device=self.device)
-                    for v in b],
-            "hid": hid,
-            "act": act,
-        }
-        # every module-path consumer (fallback, sample-sharded, autocast)
-        # keeps working; a private copy so the predictor's own stays on CPU
-        self.module = copy.deepcopy(predictor.torch_module()).to(self.device)
-        self._mlp_logged = False
-        if kc.predict_dtype == "fp64":
-            # verification mode: unrounded fit-time constants
-            eng = self.engine
-            self.mlp["bg64"] = t.tensor(
-                eng.background, dtype=t.float64, device=self.device)
-            self.mlp["wbg64"] = t.tensor(
-                eng.bg_weights, dtype=t.float64, device=self.device)
-            self.mlp["fnull64"] = t.tensor(
-                eng.fnull, dtype=t.float64, device=self.device)
-            return
-        dtype = t.bfloat16 if kc.predict_dtype == "bf16" else t.float32
-        reason = (None if kc.fused_predict
-                  else "kernels.fused_predict is off")
-        reason = reason or mlp_pack.envelope_reason(W, hid, dtype)
-        if reason is not None:
-            self._mlp_log_fallback(reason)
-            return
-        pack = mlp_pack.pack_mlp_weights(W, b, dtype, self.device)
-        bg64 = self.bg.double()
-        self.mlp["pack"] = pack
-        # fit-time constants shared by all instances
-        self.mlp["bgpart1"] = mlp_pack.group_parts(
-            pack, bg64, self.col_group, self.n_groups)      # (N, H1pad, G)
-        self.mlp["base1"] = mlp_pack.base1(pack, bg64)      # (N, H1pad)
-        self.mlp["bg_img"] = {}
-        self.mlp_fused = True
+    @property
+    def trees_kernel(self):
+        """'bits' (K4t), 'walk' (K4w) or None (module)."""
+        return (self.backend.kernel if isinstance(self.backend, TreeBackend)
+                else None)
 
-    def _mlp_log_fallback(self, reason):
-        if not self._mlp_logged:
-            logger.info(
-                "MLPPredictor runs on the torch-module path, not the fused "
-                "MLP kernel: %s", reason,
-            )
-            self._mlp_logged = True
-
-    def _mlp_forward_f64(self, rows64):
-        """fp64 torch forward from the fp64 weights."""
-        t = self.torch
-        h = rows64
-        ws, bs = self.mlp["W64"], self.mlp["b64"]
-        for w, b in zip(ws[:-1], bs[:-1]):
-            h = h @ w.T + b
-            if self.mlp["hid"] == "relu":
-                h = t.relu(h)
-            elif self.mlp["hid"] == "tanh":
-                h = t.tanh(h)
-        z = h @ ws[-1].T + bs[-1]
-        if self.mlp["act"] == "softmax":
-            return t.softmax(z, dim=-1)
-        if self.mlp["act"] == "sigmoid":
-            return t.sigmoid(z)
-        return z
-
-    def _ey_fused_mlp(self, masks, X_dev, varying):
-        """K4m: fused MLP predict. Only ey (B,S,n_out) reaches HBM; the
-        workspaces are the first-layer operand images xp1 (B,H1pad,Mpad) and
-        bgp1n (N,H1pad,Mpad), the latter cached per varying pattern."""
-        from . import mlp_pack
-
-        t = self.torch
-        b, s, m = masks.shape
-        mlp = self.mlp
-        pack = mlp["pack"]
-        vidx = t.tensor(varying, dtype=t.int64, device=self.device)
-        key = np.asarray(varying).tobytes()
-        bgp1n = mlp["bg_img"].get(key)
-        if bgp1n is None:
-            if len(mlp["bg_img"]) >= 8:
-                mlp["bg_img"].clear()
-            bgp1n = mlp_pack.first_layer_image(
-                pack, mlp["bgpart1"], vidx, negate=True)
-            mlp["bg_img"][key] = bgp1n
-        xparts = mlp_pack.group_parts(
-            pack, X_dev.double(), self.col_group, self.n_groups)
-        xp1 = mlp_pack.first_layer_image(pack, xparts, vidx)
-        ey = self._buf("ey", (b, s, self.n_out))
-        self.ext.fused_predict_mlp(
-            masks.contiguous(), xp1, bgp1n, mlp["base1"], pack["hidden_w"],
-            pack["hidden_b"], pack["wout"], pack["bout"], self.bg_w, ey,
-            mlp_pack.ACT_CODE[mlp["act"]], 0,
-        )
-        return ey
+    @property
+    def km_fused(self):
+        return (isinstance(self.backend, KernelMachineBackend)
+                and self.backend.fused)
 
     def _ey_predict_nonlinear(self, masks, X_dev, varying):
         """ey for non-linear predictors, shared by the bucket loop and the
-        sample-sharded path: the fused tree, kernel-machine or MLP kernel
-        when it applies, else the synth + torch-module path."""
-        from . import km_pack, mlp_pack
-
-        if self.trees_fused:
-            return self._ey_fused_trees(masks, X_dev, varying)
-        if self.km_fused:
-            if len(varying) <= km_pack.MAX_GROUPS:
-                return self._ey_fused_km(masks, X_dev, varying)
-            self._km_log_fallback(
-                f"{len(varying)} varying groups (supported: <= "
-                f"{km_pack.MAX_GROUPS})"
-            )
-        if self.mlp_fused:
-            if len(varying) <= mlp_pack.MAX_GROUPS:
-                return self._ey_fused_mlp(masks, X_dev, varying)
-            self._mlp_log_fallback(
-                f"{len(varying)} varying groups (supported: <= "
-                f"{mlp_pack.MAX_GROUPS})"
-            )
-        return self._ey_torch_module(masks, X_dev, varying)
-
-    def _ey_mlp_f64(self, masks, X_dev, varying, budget_bytes=256 << 20):
-        """fp64 verification path for MLPPredictor (predict_dtype='fp64'):
-        explicit masked blend + fp64 torch MLP on the SAME device masks,
-        chunked over samples like ``_ey_linear_f64``."""
-        t = self.torch
-        b, s, m = masks.shape
-        vmap = np.full(self.n_groups, m, dtype=np.int64)
-        for i, g in enumerate(varying):
-            vmap[g] = i
-        colk = t.tensor(vmap[self.engine._col_group], device=self.device)
-        bg = self.mlp["bg64"]
-        X64 = X_dev.double()
-        wbg64 = self.mlp["wbg64"]
-        width = max([self.D] + [w.shape[0] for w in self.mlp["W64"]])
-        s_chunk = max(1, budget_bytes // (8 * 3 * b * self.N * width))
-        ey = t.empty(b, s, self.n_out, dtype=t.float64, device=self.device)
-        zero_col = t.zeros(b, 1, 1, dtype=t.bool, device=self.device)
-        for lo in range(0, s, s_chunk):
-            hi = min(lo + s_chunk, s)
-            mk = masks[:, lo:hi].bool()
-            # non-varying columns map to an always-off sentinel column m
-            mk = t.cat([mk, zero_col.expand(b, hi - lo, 1)], dim=2)[:, :, colk]
-            rows = t.where(
-                mk[:, :, None, :], X64[:, None, None, :], bg[None, None, :, :]
-            )                                             # (b, sc, N, D)
-            p = self._mlp_forward_f64(rows)
-            ey[:, lo:hi] = t.einsum("bsno,n->bso", p, wbg64)
-        return ey
-
-    # ------------------------------------------------------------------ #
-    # TreeEnsemblePredictor: fused_predict_trees (K4t) with the gather
-    # traversal torch module as the out-of-envelope fallback.  A routed
-    # ensemble (tree_params() carries "routing": missing values and
-    # categorical splits) takes the same three paths: the modules and
-    # decision_bits encode raw rows themselves, the walk kernel reads rows
-    # encoded once (the background at fit, the instances per call)
-
-    def _init_trees(self, predictor):
-        from . import tree_pack
-
-        t = self.torch
-        kc = self.engine.kernels
-        if kc.predict_dtype not in ("fp32", "fp64"):
-            raise ValueError(
-                f"predict_dtype={kc.predict_dtype!r} is not available for "
-                "TreeEnsemblePredictor (a tree has nothing to round); "
-                "supported: 'fp32' (fused tree kernel) and 'fp64' "
-                "(verification)"
-            )
-        if kc.module_autocast == "bf16":
-            raise ValueError(
-                "module_autocast='bf16' is not available for "
-                "TreeEnsemblePredictor: features rounded to bf16 would flip "
-                "split decisions on the torch-module path"
-            )
-        params = predictor.tree_params()
-        # fp64 tables on the device: per-instance totals and verification
-        self.trees = {
-            "mod64": predictor.build_module(t.float64).to(self.device),
-            "act": params["activation"],
-        }
-        # every module-path consumer (fallback, sample-sharded) keeps
-        # working; a fresh module, so the caller's predictor is not touched
-        self.module = predictor.build_module().to(self.device)
-        if kc.predict_dtype == "fp64":
-            eng = self.engine
-            self.trees["bg64"] = t.tensor(
-                eng.background, dtype=t.float64, device=self.device)
-            self.trees["wbg64"] = t.tensor(
-                eng.bg_weights, dtype=t.float64, device=self.device)
-            self.trees["fnull64"] = t.tensor(
-                eng.fnull, dtype=t.float64, device=self.device)
-            return
-        reason = (None if kc.fused_predict
-                  else "kernels.fused_predict is off")
-        walk = False
-        if reason is None:
-            reason = tree_pack.envelope_reason(params)
-            if reason is not None:
-                # beyond one u64 of split decisions per tree: the walk kernel
-                walk_reason = tree_pack.walk_envelope_reason(
-                    params, self.D, self.n_groups)
-                walk = walk_reason is None
-                reason = None if walk else f"{reason}; {walk_reason}"
-        if reason is not None:
-            # fit time only, so the reason is logged once per engine
-            logger.info(
-                "TreeEnsemblePredictor runs on the torch-module path, "
-                "not the fused tree kernel: %s", reason,
-            )
-            return
-        if walk:
-            self.trees["pack"] = tree_pack.pack_trees_walk(
-                params, self.engine._col_group, self.device)
-            # routed tables: the background as the nodes see it
-            self.trees["bg_enc"] = tree_pack.encode_rows(
-                self.trees["pack"], self.bg)
-            self.trees_fused = True
-            self.trees_kernel = "walk"
-            return
-        pack = tree_pack.pack_trees(params, self.engine._col_group, self.device)
-        self.trees["pack"] = pack
-        # fit-time constant shared by all instances: the background rows'
-        # split decisions, one u64 per (row, tree)
-        self.trees["dbg"] = tree_pack.decision_bits(pack, self.bg)
-        self.trees_fused = True
-        self.trees_kernel = "bits"
-
-    def _ey_fused_trees(self, masks, X_dev, varying):
-        """K4t / K4w: fused tree predict. Only ey (B,S,n_out) reaches HBM;
-        the per-call operands are the group -> varying-index table and, for
-        the bit-register kernel, the instances' packed decisions dx (B,T)."""
-        from . import tree_pack
-
-        t = self.torch
-        b, s, m = masks.shape
-        pack = self.trees["pack"]
-        vmap_h = np.full(self.n_groups, -1, dtype=np.int32)
-        vmap_h[np.asarray(varying)] = np.arange(m, dtype=np.int32)
-        vmap = t.tensor(vmap_h, device=self.device)
-        ey = self._buf("ey", (b, s, self.n_out))
-        if self.trees_kernel == "walk":
-            # K4w reads the float32 rows themselves (encoded, for routed
-            # tables): no decision bits
-            return tree_pack.fused_predict_walk(
-                self.ext, pack, masks.contiguous(), vmap,
-                tree_pack.encode_rows(pack, X_dev), self.trees["bg_enc"],
-                self.bg_w, ey,
-            )
-        dx = tree_pack.decision_bits(pack, X_dev)
-        return tree_pack.fused_predict(
-            self.ext, pack, masks.contiguous(), vmap, dx, self.trees["dbg"],
-            self.bg_w, ey,
-        )
-
-    def _ey_trees_f64(self, masks, X_dev, varying, budget_bytes=256 << 20):
-        """fp64 verification path for TreeEnsemblePredictor
-        (predict_dtype='fp64'): explicit masked blend + fp64 gather
-        traversal on the SAME device masks, chunked like ``_ey_mlp_f64``."""
-        t = self.torch
-        b, s, m = masks.shape
-        vmap = np.full(self.n_groups, m, dtype=np.int64)
-        for i, g in enumerate(varying):
-            vmap[g] = i
-        colk = t.tensor(vmap[self.engine._col_group], device=self.device)
-        bg = self.trees["bg64"]
-        X64 = X_dev.double()
-        wbg64 = self.trees["wbg64"]
-        n_trees = self.trees["mod64"].roots.shape[0]
-        width = max(self.D, 4 * n_trees)
-        s_chunk = max(1, budget_bytes // (8 * 3 * b * self.N * width))
-        ey = t.empty(b, s, self.n_out, dtype=t.float64, device=self.device)
-        zero_col = t.zeros(b, 1, 1, dtype=t.bool, device=self.device)
-        for lo in range(0, s, s_chunk):
-            hi = min(lo + s_chunk, s)
-            mk = masks[:, lo:hi].bool()
-            # non-varying columns map to an always-off sentinel column m
-            mk = t.cat([mk, zero_col.expand(b, hi - lo, 1)], dim=2)[:, :, colk]
-            rows = t.where(
-                mk[:, :, None, :], X64[:, None, None, :], bg[None, None, :, :]
-            )                                             # (b, sc, N, D)
-            with t.no_grad():
-                p = self.trees["mod64"](rows.reshape(-1, self.D))
-            p = p.view(b, hi - lo, self.N, self.n_out)
-            ey[:, lo:hi] = t.einsum("bsno,n->bso", p, wbg64)
-        return ey
-
-    # ------------------------------------------------------------------ #
-    # KernelMachinePredictor: fused_predict_kernelmachine (K4k) with the
-    # GEMM-form torch module as the out-of-envelope fallback.
-    # MulticlassSVCPredictor comes through the same hook: its "ovr" and
-    # "coupling" activations launch fused_predict_kernelmachine_pairs (K4kp)
-    # from km_pack.fused_predict, and ey has n_out = K columns
-
-    def _init_kernel_machine(self, predictor):
-        from . import km_pack
-
-        t = self.torch
-        kc = self.engine.kernels
-        if kc.predict_dtype not in ("fp32", "fp64"):
-            raise ValueError(
-                f"predict_dtype={kc.predict_dtype!r} is not available for "
-                "KernelMachinePredictor (a bf16 distance under an "
-                "exponential is not a usable mode); supported: 'fp32' "
-                "(fused kernel-machine kernel) and 'fp64' (verification)"
-            )
-        if kc.module_autocast == "bf16":
-            raise ValueError(
-                "module_autocast='bf16' is not available for "
-                "KernelMachinePredictor: the distance expansion on the "
-                "torch-module path cancels, and bf16 leaves nothing of it"
-            )
-        params = predictor.kernel_machine_params()
-        # fp64 module on the device: per-instance totals and verification
-        self.km = {
-            "mod64": predictor.build_module(t.float64).to(self.device),
-            "act": params["activation"],
-            "n_sv": int(np.asarray(params["alpha"]).shape[1]),
-        }
-        # every module-path consumer (fallback, sample-sharded) keeps
-        # working; a fresh module, so the caller's predictor is not touched
-        self.module = predictor.build_module().to(self.device)
-        self._km_logged = False
-        if kc.predict_dtype == "fp64":
-            eng = self.engine
-            self.km["bg64"] = t.tensor(
-                eng.background, dtype=t.float64, device=self.device)
-            self.km["wbg64"] = t.tensor(
-                eng.bg_weights, dtype=t.float64, device=self.device)
-            self.km["fnull64"] = t.tensor(
-                eng.fnull, dtype=t.float64, device=self.device)
-            return
-        reason = (None if kc.fused_predict
-                  else "kernels.fused_predict is off")
-        reason = reason or km_pack.envelope_reason(params)
-        if reason is not None:
-            self._km_log_fallback(reason)
-            return
-        pack = km_pack.pack_machine(
-            params, self.engine._col_group, self.n_groups, self.device)
-        self.km["pack"] = pack
-        # fit-time constants shared by all instances
-        self.km["bgparts"] = km_pack.group_parts(pack, self.bg.double())  # (N,V,G)
-        self.km["base"] = km_pack.base(pack, self.km["bgparts"])          # (N,Vpad)
-        self.km["bg_img"] = {}
-        self.km_fused = True
-
-    def _km_log_fallback(self, reason):
-        if not self._km_logged:
-            logger.info(
-                "KernelMachinePredictor runs on the torch-module path, not "
-                "the fused kernel-machine kernel: %s", reason,
-            )
-            self._km_logged = True
-
-    def _ey_fused_km(self, masks, X_dev, varying):
-        """K4k: fused kernel-machine predict. Only ey (B,S,n_out) reaches
-        HBM; the workspaces are the operand images xp (B,Vpad,Mpad) and
-        bgpn (N,Vpad,Mpad), the latter cached per varying pattern. The
-        bucket is split along B so that one launch's workspaces stay within
-        ``km_pack.WORKSPACE_BYTES``."""
-        from . import km_pack
-
-        t = self.torch
-        b, s, m = masks.shape
-        km = self.km
-        pack = km["pack"]
-        vidx = t.tensor(varying, dtype=t.int64, device=self.device)
-        key = np.asarray(varying).tobytes()
-        bgpn = km["bg_img"].get(key)
-        if bgpn is None:
-            if len(km["bg_img"]) >= 8:
-                km["bg_img"].clear()
-            bgpn = km_pack.image(pack, km["bgparts"], vidx, negate=True)
-            km["bg_img"][key] = bgpn
-        masks = masks.contiguous()
-        ey = self._buf("ey", (b, s, self.n_out))
-        step = km_pack.instances_per_launch(pack, self.D, m)
-        X64 = X_dev.double()
-        for lo in range(0, b, step):
-            hi = min(lo + step, b)
-            xp = km_pack.image(
-                pack, km_pack.group_parts(pack, X64[lo:hi]), vidx)
-            km_pack.fused_predict(
-                self.ext, pack, masks[lo:hi], xp, bgpn, km["base"],
-                self.bg_w, ey[lo:hi])
-        return ey
-
-    def _ey_km_f64(self, masks, X_dev, varying, budget_bytes=256 << 20):
-        """fp64 verification path for KernelMachinePredictor
-        (predict_dtype='fp64'): explicit masked blend + the fp64 module on
-        the SAME device masks, chunked like ``_ey_mlp_f64``."""
-        t = self.torch
-        b, s, m = masks.shape
-        vmap = np.full(self.n_groups, m, dtype=np.int64)
-        for i, g in enumerate(varying):
-            vmap[g] = i
-        colk = t.tensor(vmap[self.engine._col_group], device=self.device)
-        bg = self.km["bg64"]
-        X64 = X_dev.double()
-        wbg64 = self.km["wbg64"]
-        width = max(self.D, self.km["n_sv"])
-        s_chunk = max(1, budget_bytes // (8 * 3 * b * self.N * width))
-        ey = t.empty(b, s, self.n_out, dtype=t.float64, device=self.device)
-        zero_col = t.zeros(b, 1, 1, dtype=t.bool, device=self.device)
-        for lo in range(0, s, s_chunk):
-            hi = min(lo + s_chunk, s)
-            mk = masks[:, lo:hi].bool()
-            # non-varying columns map to an always-off sentinel column m
-            mk = t.cat([mk, zero_col.expand(b, hi - lo, 1)], dim=2)[:, :, colk]
-            rows = t.where(
-                mk[:, :, None, :], X64[:, None, None, :], bg[None, None, :, :]
-            )                                             # (b, sc, N, D)
-            with t.no_grad():
-                p = self.km["mod64"](rows.reshape(-1, self.D))
-            p = p.view(b, hi - lo, self.N, self.n_out)
-            ey[:, lo:hi] = t.einsum("bsno,n->bso", p, wbg64)
+        sample-sharded path: the backend's fused kernel when it applies,
+        else the synth + torch-module path."""
+        ey = None
+        if self.backend is not None and self.backend.fused:
+            ey = self.backend.ey_fused(masks, X_dev, varying)
+        if ey is None:
+            ey = self._ey_torch_module(masks, X_dev, varying)
         return ey
 
     # ------------------------------------------------------------------ #
@@ -649,14 +249,8 @@ class GpuKernelShap:
             if a == 2:
                 return t.softmax(z, dim=-1)
             return z
-        if self.mlp is not None:
-            return self._mlp_forward_f64(rows.double())
-        if self.trees is not None:
-            with t.no_grad():
-                return self.trees["mod64"](rows)
-        if self.km is not None:
-            with t.no_grad():
-                return self.km["mod64"](rows)
+        if self.backend is not None:
+            return self.backend.forward_f64(rows)
         with t.no_grad():
             return self.module(rows).double()
 
@@ -741,6 +335,16 @@ class GpuKernelShap:
 
     # ------------------------------------------------------------------ #
 
+    # route names of ``routes`` -> the linear predict wrappers below
+    _LINEAR_EY = {
+        "u8": "_ey_fused_linear", "bf16": "_ey_fused_bf16",
+        "tiled": "_ey_fused_tiled", "tiled_bf16": "_ey_fused_tiled_bf16",
+        "torch": "_ey_linear_torch",
+    }
+
+    def _linear_ey(self, route):
+        return getattr(self, self._LINEAR_EY[route])
+
     def _diff_tensor(self, X_dev, varying, vidx_t=None):
         """diff[b, o, k, n] = x_part[b, k, o] - bg_part[n, k, o] over varying
         groups k (the algebraically folded masked-background blend)."""
@@ -754,27 +358,25 @@ class GpuKernelShap:
     def _ey_fused_linear(self, masks, X_dev, varying, vidx_t=None):
         """K3-K6 fused MFMA path (linear predictor, Mpad<=64, Npad<=128).
         The A operand is converted in-register from the raw u8 masks."""
-        t = self.torch
         b, s, m = masks.shape
-        mpad = max(4, (m + 3) // 4 * 4)
-        npad = (self.N + 15) // 16 * 16
-        if vidx_t is None:
-            vidx_t = t.tensor(varying, dtype=t.int64, device=self.device)
-        act, oimg = self._act_oimg()
+        c, vidx_t = self._linear_consts(), self._vidx(varying, vidx_t)
         # pad slots are zeroed once at allocation and never written after
         # (buffer name keyed by m so a different varying count cannot see
         # stale values)
-        diff = self._buf(f"diff{m}", (b, oimg, mpad, npad), zeroed=True)
+        diff = self._buf(
+            f"diff{m}", (b, c["oimg"], routes.pad_m(m), c["npad"]), zeroed=True)
         self.ext.build_diff_f32(
-            self._x_part_img(X_dev, act), self._bg_part_img(act), vidx_t, diff
-        )
-        base = t.zeros(oimg, npad, device=self.device)
-        base[:, : self.N] = self._base_img(act)
-        wbg = t.zeros(npad, device=self.device)
-        wbg[: self.N] = self.bg_w
+            self._x_part_img(X_dev, c["act"]), c["bgp"], vidx_t, diff)
         ey = self._buf("ey", (b, s, self.n_out))
-        self.ext.fused_predict_linear(masks, diff, base, wbg, ey, act)
+        self.ext.fused_predict_linear(
+            masks, diff, c["base"], c["wbg"], ey, c["act"])
         return ey
+
+    def _vidx(self, varying, vidx_t=None):
+        if vidx_t is not None:
+            return vidx_t
+        return self.torch.tensor(varying, dtype=self.torch.int64,
+                                 device=self.device)
 
     def _act_oimg(self):
         """Binary softmax runs on the logit DIFFERENCE (one operand image,
@@ -790,45 +392,50 @@ class GpuKernelShap:
             return (xp[:, :, 1:2] - xp[:, :, 0:1]).contiguous()
         return xp
 
-    def _bg_part_img(self, act):
-        if act == 3:
-            if not hasattr(self, "_bg_part_d"):
-                self._bg_part_d = (
-                    self.bg_part[:, :, 1:2] - self.bg_part[:, :, 0:1]
-                ).contiguous()
-            return self._bg_part_d
-        return self.bg_part
+    def _linear_consts(self):
+        """Operands of the linear predict kernels (u8-mask and packed) that
+        depend only on the fitted engine, built once: the background part
+        image, the padded base / wbg images and the link of fnull (fp64 for
+        the totals, fp32 for ey)."""
+        c = getattr(self, "_linear_c", None)
+        if c is None:
+            t = self.torch
+            act, oimg = self._act_oimg()
+            npad = routes.pad_n(self.N)
+            bgp, base_img = self.bg_part, self.baseN.T
+            if act == 3:
+                bgp = bgp[:, :, 1:2] - bgp[:, :, 0:1]
+                base_img = (self.baseN[:, 1] - self.baseN[:, 0])[None, :]
+            base = t.zeros(oimg, npad, device=self.device)
+            base[:, : self.N] = base_img
+            wbg = t.zeros(npad, device=self.device)
+            wbg[: self.N] = self.bg_w
+            lfnull64 = self._link(self.fnull.double()).contiguous()
+            c = self._linear_c = {
+                "act": act, "oimg": oimg, "npad": npad, "base": base,
+                "wbg": wbg, "lfnull64": lfnull64,
+                "lfnull": lfnull64.float().contiguous(),
+                "bgp": bgp.contiguous(),
+                "link": 0 if self.link_name == "identity" else 1,
+            }
+        return c
 
-    def _base_img(self, act):
-        if act == 3:
-            return (self.baseN[:, 1] - self.baseN[:, 0])[None, :]
-        return self.baseN.T
-
-    def _ey_fused_bf16(self, masks, X_dev, varying, vidx_t=None, packed=None):
+    def _ey_fused_bf16(self, masks, X_dev, varying, vidx_t=None):
         """bf16 matrix-core predict (predict_dtype 'bf16x2'/'bf16'): one
         v_mfma_f32_16x16x32_bf16 spans the whole K dim; 'bf16x2' adds a lo
         correction image (B = hi + lo) for fp32-grade accuracy."""
-        t = self.torch
         b, s, m = masks.shape
-        npad = (self.N + 15) // 16 * 16
+        c, vidx_t = self._linear_consts(), self._vidx(varying, vidx_t)
         split = 2 if self.engine.kernels.predict_dtype == "bf16x2" else 1
-        if packed is not None:
-            self.ext.pack_masks(masks, packed)   # graph-path convenience
-        if vidx_t is None:
-            vidx_t = t.tensor(varying, dtype=t.int64, device=self.device)
-        act, oimg = self._act_oimg()
         diffB = self._buf(
-            f"diffB{m}", (b, split, oimg, npad, 40), t.bfloat16, zeroed=True
+            f"diffB{m}", (b, split, c["oimg"], c["npad"], 40),
+            self.torch.bfloat16, zeroed=True,
         )
         self.ext.build_diff_bf16(
-            self._x_part_img(X_dev, act), self._bg_part_img(act), vidx_t, diffB
-        )
-        base = t.zeros(oimg, npad, device=self.device)
-        base[:, : self.N] = self._base_img(act)
-        wbg = t.zeros(npad, device=self.device)
-        wbg[: self.N] = self.bg_w
+            self._x_part_img(X_dev, c["act"]), c["bgp"], vidx_t, diffB)
         ey = self._buf("ey", (b, s, self.n_out))
-        self.ext.fused_predict_bf16(masks, diffB, base, wbg, ey, act)
+        self.ext.fused_predict_bf16(
+            masks, diffB, c["base"], c["wbg"], ey, c["act"])
         return ey
 
     def _ey_fused_tiled(self, masks, X_dev, varying, vidx_t=None):
@@ -836,27 +443,20 @@ class GpuKernelShap:
         Npad>128): diff streamed through LDS in
         (k-chunk x 128-col) tiles, per-column-tile partial reductions summed
         by a deterministic second kernel (no float atomics)."""
-        t = self.torch
         b, s, m = masks.shape
+        c, vidx_t = self._linear_consts(), self._vidx(varying, vidx_t)
         # Mpad rounds to the kernel's 16-deep LDS k-chunks so the inner MFMA
         # loop is fully unrolled (pad k-slices are zeros in the diff image)
         mpad = max(16, (m + 15) // 16 * 16)
-        npad = (self.N + 15) // 16 * 16
-        if vidx_t is None:
-            vidx_t = t.tensor(varying, dtype=t.int64, device=self.device)
-        act, oimg = self._act_oimg()
-        diff = self._buf(f"difft{m}", (b, oimg, mpad, npad), zeroed=True)
+        diff = self._buf(
+            f"difft{m}", (b, c["oimg"], mpad, c["npad"]), zeroed=True)
         self.ext.build_diff_f32(
-            self._x_part_img(X_dev, act), self._bg_part_img(act), vidx_t, diff
-        )
-        base = t.zeros(oimg, npad, device=self.device)
-        base[:, : self.N] = self._base_img(act)
-        wbg = t.zeros(npad, device=self.device)
-        wbg[: self.N] = self.bg_w
-        n_ntiles = (npad + 127) // 128
-        partial = self._buf("ftpart", (b, n_ntiles, s, self.n_out))
+            self._x_part_img(X_dev, c["act"]), c["bgp"], vidx_t, diff)
+        partial = self._buf(
+            "ftpart", (b, (c["npad"] + 127) // 128, s, self.n_out))
         ey = self._buf("ey", (b, s, self.n_out))
-        self.ext.fused_predict_tiled(masks, diff, base, wbg, partial, ey, act)
+        self.ext.fused_predict_tiled(
+            masks, diff, c["base"], c["wbg"], partial, ey, c["act"])
         return ey
 
     def _ey_linear_f64(self, masks, X_dev, varying, s_chunk=2048):
@@ -907,32 +507,21 @@ class GpuKernelShap:
         stress shapes): one v_mfma_f32_16x16x32_bf16 per 32-deep k block —
         8x the f32 MFMA rate — with the hi+lo split B operand for
         fp32-grade results ('bf16x2')."""
-        t = self.torch
         b, s, m = masks.shape
+        c, vidx_t = self._linear_consts(), self._vidx(varying, vidx_t)
         mpad = max(32, (m + 31) // 32 * 32)     # FTB_KC contract
-        npad = (self.N + 15) // 16 * 16
-        if vidx_t is None:
-            vidx_t = t.tensor(varying, dtype=t.int64, device=self.device)
-        act, oimg = self._act_oimg()
         split = 2 if self.engine.kernels.predict_dtype == "bf16x2" else 1
         diffb = self._buf(
-            f"difftb{m}", (b, split, oimg, npad, mpad), t.bfloat16,
-            zeroed=True,
+            f"difftb{m}", (b, split, c["oimg"], c["npad"], mpad),
+            self.torch.bfloat16, zeroed=True,
         )
         self.ext.build_diff_bf16_tiled(
-            self._x_part_img(X_dev, act), self._bg_part_img(act), vidx_t,
-            diffb,
-        )
-        base = t.zeros(oimg, npad, device=self.device)
-        base[:, : self.N] = self._base_img(act)
-        wbg = t.zeros(npad, device=self.device)
-        wbg[: self.N] = self.bg_w
-        n_ntiles = (npad + 127) // 128
-        partial = self._buf("ftpart", (b, n_ntiles, s, self.n_out))
+            self._x_part_img(X_dev, c["act"]), c["bgp"], vidx_t, diffb)
+        partial = self._buf(
+            "ftpart", (b, (c["npad"] + 127) // 128, s, self.n_out))
         ey = self._buf("ey", (b, s, self.n_out))
         self.ext.fused_predict_tiled_bf16(
-            masks, diffb, base, wbg, partial, ey, act
-        )
+            masks, diffb, c["base"], c["wbg"], partial, ey, c["act"])
         return ey
 
     def _ey_linear_torch(self, masks, X_dev, varying, s_chunk=4096):
@@ -1023,43 +612,10 @@ class GpuKernelShap:
     # packed linear pipeline: four kernels from X to phi_full
 
     def _packed_ok(self, m, plan, l1_reg) -> bool:
-        """Whether a bucket of ``m`` varying groups runs the packed pipeline
-        (K2p, K0p, K3p, K7p). Everything else keeps the u8-mask path."""
-        kc = self.engine.kernels
-        return (
-            self.linear is not None
-            and kc.predict_dtype == "fp32"
-            and kc.fused_predict
-            and kc.wls_mode in ("auto", "mfma")
-            and 2 <= m <= 64
-            and (self.N + 15) // 16 * 16 <= 128
-            and self.n_out in (1, 2, 4)
-            and (m - 1) + self.n_out <= 16
-            and not self._l1_active(plan, l1_reg)
-        )
-
-    def _packed_consts(self):
-        """Operands that depend only on the fitted engine: padded base / wbg
-        images and the link of fnull (fp64 for the totals, fp32 for ey)."""
-        c = getattr(self, "_packed_c", None)
-        if c is None:
-            t = self.torch
-            act, oimg = self._act_oimg()
-            npad = (self.N + 15) // 16 * 16
-            base = t.zeros(oimg, npad, device=self.device)
-            base[:, : self.N] = self._base_img(act)
-            wbg = t.zeros(npad, device=self.device)
-            wbg[: self.N] = self.bg_w
-            lfnull64 = self._link(self.fnull.double()).contiguous()
-            c = {
-                "act": act, "oimg": oimg, "npad": npad, "base": base,
-                "wbg": wbg, "lfnull64": lfnull64,
-                "lfnull": lfnull64.float().contiguous(),
-                "bgp": self._bg_part_img(act).contiguous(),
-                "link": 0 if self.link_name == "identity" else 1,
-            }
-            self._packed_c = c
-        return c
+        """``routes.packed_ok`` for a bucket of ``m`` varying groups."""
+        return routes.packed_ok(
+            self.engine.kernels, self.linear is not None, m, self.N,
+            self.n_out, self._l1_active(plan, l1_reg))
 
     def _packed_plan(self, plan):
         """Per-plan operands: enumerated rows as packed words, the (S,)
@@ -1108,9 +664,9 @@ class GpuKernelShap:
         t = self.torch
         b = X_dev.shape[0]
         m, s = plan.m, plan.nsamples
-        c = self._packed_consts()
+        c = self._linear_consts()
         enum_packed, kw, cdf, szs = self._packed_plan(plan)
-        mpad = max(4, (m + 3) // 4 * 4)
+        mpad = routes.pad_m(m)
         packed = self._buf("packed", (b, s), t.int64)
         self.ext.fill_masks_packed(
             packed, enum_packed, plan.n_random, cdf, szs,
@@ -1155,14 +711,10 @@ class GpuKernelShap:
         total = (lfx - lfnull64[None, :]).float().contiguous()
         lfnull = lfnull64.float()
         masks, kw = self._device_masks(plan, np.arange(b), ids_dev=ids_dev)
-        kc = self.engine.kernels
         packed = self._buf("packed", (b, plan.nsamples), t.int64)
         self.ext.pack_masks(masks, packed)
-        if (kc.predict_dtype in ("bf16", "bf16x2") and m <= 32
-                and self.n_out in (1, 2, 4)):
-            ey = self._ey_fused_bf16(masks, X_dev, varying, vidx_t, packed=None)
-        else:
-            ey = self._ey_fused_linear(masks, X_dev, varying, vidx_t)
+        route = routes.graph_predict_route(self.engine.kernels, m, self.n_out)
+        ey = self._linear_ey(route)(masks, X_dev, varying, vidx_t)
         if self.link_name == "identity":
             ey_adj = ey.sub_(lfnull[None, None, :])
         else:
@@ -1245,36 +797,26 @@ class GpuKernelShap:
 
         s = nsamples or default_nsamples(max(2, self.n_groups))
         g = self.n_groups
+        npad = routes.pad_n(self.N)
         if g >= 2 and self._packed_ok(g, self.engine._plan(g, nsamples),
                                       l1_reg):
             # packed pipeline (eligible at g groups, hence at any smaller
             # varying count): packed u64 + ey f32 per sample, no u8 masks
             # and no weight broadcast; diff image and totals per instance
-            npad = (self.N + 15) // 16 * 16
             per_inst = (s * (8 + 4 * self.n_out)
                         + 4 * self.n_out * (g + 3) * npad + (1 << 14))
             return max(1, self._CHUNK_BYTES // per_inst)
         # masks u8 + packed u64 + kwb f32 + ey f32 (+ column-tile partials
         # on the tiled stress path) per instance
-        npad = (self.N + 15) // 16 * 16
         n_ntiles = (npad + 127) // 128
         per_inst = s * (g + 8 + 4 + 4 * self.n_out) + (1 << 14)
         if g > 64 or npad > 128:
             per_inst += s * 4 * self.n_out * n_ntiles        # ftpart
-            mpad = max(4, (g + 3) // 4 * 4)
-            per_inst += 4 * mpad * npad * max(1, self.n_out) # diff image
+            per_inst += (4 * routes.pad_m(g) * npad
+                         * max(1, self.n_out))               # diff image
             per_inst += 8 * g * (g + self.n_out) * 2         # Gram + LU work
-        if self.mlp_fused:
-            # fused MLP workspaces: fp64 group parts (D x G indicator product
-            # and H1pad x G result) + the xp1 operand image (H1pad x Mpad)
-            h1 = self.mlp["pack"]["hpad"][0]
-            per_inst += 8 * g * (self.D + 2 * h1) + 4 * h1 * (g + 31)
-        if self.trees_kernel == "bits":
-            # packed decisions dx plus the (T, 64) comparison image behind them
-            # (the walk kernel reads x itself and has no per-instance workspace)
-            per_inst += self.trees["pack"]["n_trees"] * (8 + 64 * 9)
-        # (the fused kernel-machine workspaces are bounded per launch,
-        # km_pack.WORKSPACE_BYTES, not per instance)
+        if self.backend is not None:
+            per_inst += self.backend.workspace_bytes_per_instance(g)
         return max(1, self._CHUNK_BYTES // per_inst)
 
     def shap_values(
@@ -1392,9 +934,7 @@ class GpuKernelShap:
         # per-instance totals and the result buffer: computed only once the
         # speculative replay (which carries its own) is out of the picture
         X64_dev = None
-        f64c = next((c for c in (self.mlp, self.trees, self.km)
-                     if c is not None), None)
-        if fp64 and f64c is not None:
+        if fp64 and self.backend is not None:
             # MLP / tree / kernel-machine verification mode: inputs stay fp64 end to end (the
             # fp32 rounding of x alone shifts phi by ~1e-7)
             X64_dev = (X.to(self.device).double() if t.is_tensor(X)
@@ -1403,7 +943,7 @@ class GpuKernelShap:
             X_dev if X64_dev is None else X64_dev)
         lfx = self._link(fx)
         lfnull64 = self._link(
-            self.fnull.double() if X64_dev is None else f64c["fnull64"])
+            self.fnull.double() if X64_dev is None else self.backend.fnull64)
         total_all = (lfx - lfnull64[None, :])           # (B, n_out) fp64
         if not fp64:
             total_all = total_all.float()
@@ -1440,37 +980,29 @@ class GpuKernelShap:
         timer.mark("bucket")
 
         kc = self.engine.kernels
-        if self._graphs_enabled and not fp64 and uniq.shape[0] == 1 \
-                and self.linear is not None \
-                and kc.fused_predict and kc.wls_mode in ("auto", "mfma"):
+        if self._graphs_enabled and not fp64 and uniq.shape[0] == 1:
             varying0 = np.nonzero(uniq[0])[0]
             m0 = len(varying0)
-            if m0 >= 2:
-                plan0 = self.engine._plan(m0, nsamples)
-                mpad0 = max(4, (m0 + 3) // 4 * 4)
-                npad0 = (self.N + 15) // 16 * 16
-                if (
-                    mpad0 <= 64
-                    and npad0 <= 128
-                    and self.n_out in (1, 2, 4)
-                    and not self._l1_active(plan0, l1_reg)
-                ):
-                    out = self._graph_explain(
-                        X_dev, plan0, varying0, instance_offset,
-                        as_tensor=as_tensor,
+            plan0 = self.engine._plan(m0, nsamples) if m0 >= 2 else None
+            if plan0 is not None and routes.graph_ok(
+                    kc, self.linear is not None, m0, self.N, self.n_out,
+                    self._l1_active(plan0, l1_reg)):
+                out = self._graph_explain(
+                    X_dev, plan0, varying0, instance_offset,
+                    as_tensor=as_tensor,
+                )
+                if out is not None:
+                    key0 = 0
+                    for g in varying0:
+                        key0 |= 1 << int(g)
+                    self._spec = (
+                        key0,
+                        (b, plan0.nsamples, varying0.tobytes(),
+                         int(instance_offset)),
+                        m0,
                     )
-                    if out is not None:
-                        key0 = 0
-                        for g in varying0:
-                            key0 |= 1 << int(g)
-                        self._spec = (
-                            key0,
-                            (b, plan0.nsamples, varying0.tobytes(),
-                             int(instance_offset)),
-                            m0,
-                        )
-                        timer.mark("graph")
-                        return out
+                    timer.mark("graph")
+                    return out
 
         for u in range(uniq.shape[0]):
             varying = np.nonzero(uniq[u])[0]
@@ -1523,83 +1055,22 @@ class GpuKernelShap:
             if m <= 64:
                 # packed u64 masks feed the MFMA WLS Gram build
                 packed = self._buf("packed", (len(ids), plan.nsamples), t.int64)
+                self.ext.pack_masks(masks, packed)
             pairwise = False
             if self.linear is not None:
-                act3 = self._act_oimg()[0] == 3
-                mpad = max(4, (m + 3) // 4 * 4)
-                npad = (self.N + 15) // 16 * 16
-                use_bf16 = (
-                    kc.predict_dtype in ("bf16", "bf16x2")
-                    and m <= 32 and npad <= 128 and self.n_out in (1, 2, 4)
-                )
-                if packed is not None:
-                    self.ext.pack_masks(masks, packed)
-                split = 2 if kc.predict_dtype == "bf16x2" else 1
-                bf16_tiled_ok = (
-                    kc.predict_dtype in ("bf16", "bf16x2")
-                    and split * (1 if act3 else self.n_out) * 128 * 40 * 2
-                        <= 64 * 1024
-                )
-                if kc.fused_predict and use_bf16:
-                    ey = self._ey_fused_bf16(masks, sub_X, varying, packed=None)
-                elif (kc.fused_predict and kc.predict_dtype == "fp32"
-                        and mpad <= 64 and npad <= 128
-                        and self.n_out in (1, 2, 4)):
-                    ey = self._ey_fused_linear(masks, sub_X, varying)
-                elif (kc.fused_predict and bf16_tiled_ok
-                        and self.n_out in (1, 2, 4)):
-                    # bf16 matrix-core tiled path (opt-in dtype), any shape
-                    ey = self._ey_fused_tiled_bf16(masks, sub_X, varying)
-                    pairwise = act3
-                elif kc.fused_predict and self.n_out in (1, 2, 4):
-                    # stress shapes stay on the hand-written MFMA path; the
-                    # tiled kernel dual-accumulates (p0, p1) so the pairwise
-                    # logit survives saturated probabilities
-                    ey = self._ey_fused_tiled(masks, sub_X, varying)
-                    pairwise = act3
-                else:
-                    ey = self._ey_linear_torch(masks, sub_X, varying)
-                    pairwise = act3  # torch softmax is relatively accurate
+                # the tiled kernels dual-accumulate (p0, p1), and torch's
+                # softmax is relatively accurate: the pairwise logit survives
+                # saturated probabilities there
+                route, pairwise = routes.linear_predict_route(
+                    kc, m, self.N, self.n_out, self._act_oimg()[0] == 3)
+                ey = self._linear_ey(route)(masks, sub_X, varying)
             else:
-                if packed is not None:
-                    self.ext.pack_masks(masks, packed)
                 ey = self._ey_predict_nonlinear(masks, sub_X, varying)
             timer.mark("predict")
             ey_adj = self._link_ey(ey, lfnull, pairwise)
-            total = total_all[ids_t].contiguous()
-            if self._l1_active(plan, l1_reg):
-                if kc.l1_device:
-                    support, g64, r64 = self._l1_select_batched(
-                        masks, kw, ey_adj, l1_reg
-                    )
-                    phi = self._solve_selected(
-                        masks, kw, ey_adj, total, support, g64, r64
-                    )
-                else:
-                    phi = self._solve_host_l1(masks, kw, ey_adj, total, l1_reg)
-            else:
-                phi = self._buf("phi", (len(ids), m, self.n_out))
-                # fp32 Gram conditioning degrades with M (Shapley kernel
-                # weights span orders of magnitude): MFMA path covers
-                # (M-1)+n_out <= 16; the scalar fp32 kernel up to M=24;
-                # larger M goes to the fp64 batched torch solve
-                use_kernel = (
-                    kc.wls_mode != "torch"
-                    and 2 <= m
-                    and self.n_out <= 8
-                    and (m - 1 + self.n_out <= 16 or m <= 24)
-                )
-                if use_kernel:
-                    # wls_mode 'generic' disables the MFMA Gram build by
-                    # withholding the packed masks
-                    pk = None if kc.wls_mode == "generic" else packed
-                    self.ext.wls_solve(masks, kw, ey_adj, total, phi, pk)
-                elif (kc.wls_mode in ("auto", "mfma") and m <= 513
-                        and self.n_out <= 8):
-                    # stress shapes: MFMA-tiled Gram build + fp64 solve
-                    phi = self._solve_gram(masks, kw, ey_adj, total)
-                else:
-                    phi = self._solve_torch(masks, kw, ey_adj, total)
+            phi = self._solve_bucket(
+                plan, masks, packed, kw, ey_adj,
+                total_all[ids_t].contiguous(), l1_reg)
             timer.mark("wls")
             vidx_t = t.tensor(varying, dtype=t.int64, device=self.device)
             phi_full[ids_t[:, None], vidx_t[None, :]] = phi
@@ -1713,20 +1184,15 @@ class GpuKernelShap:
         device masks, exact fp64 kernel weights (rebuilt from the plan's
         fp64 arrays, not the fp32 device copy), fp64 link and WLS."""
         t = self.torch
-        if self.linear is None and self.mlp is None and self.trees is None \
-                and self.km is None:
+        if self.linear is None and self.backend is None:
             raise TypeError(
                 "predict_dtype='fp64' is the linear-predictor verification "
                 "mode; torch-module predictors have no fp64 reference "
                 "(convert the module to double and use device='cpu' instead)."
             )
         b = sub_X.shape[0]
-        if self.mlp is not None:
-            ey = self._ey_mlp_f64(masks, sub_X, varying)
-        elif self.trees is not None:
-            ey = self._ey_trees_f64(masks, sub_X, varying)
-        elif self.km is not None:
-            ey = self._ey_km_f64(masks, sub_X, varying)
+        if self.backend is not None:
+            ey = self.backend.ey_f64(masks, sub_X, varying)
         else:
             ey = self._ey_linear_f64(masks, sub_X, varying)
         kw64 = t.from_numpy(
@@ -1754,6 +1220,31 @@ class GpuKernelShap:
         if self._l1_active(plan, l1_reg):
             return self._solve_host_l1(masks, kw, ey_adj, total, l1_reg).double()
         return self._solve_torch(masks, kw, ey_adj, total, out_dtype=t.float64)
+
+    def _solve_bucket(self, plan, masks, packed, kw, ey_adj, total, l1_reg):
+        """phi (b, m, n_out) of one u8-mask bucket: l1 pre-selection when it
+        is active, else the solver ``routes.wls_route`` names."""
+        kc = self.engine.kernels
+        b, _, m = masks.shape
+        if self._l1_active(plan, l1_reg):
+            if not kc.l1_device:
+                return self._solve_host_l1(masks, kw, ey_adj, total, l1_reg)
+            support, g64, r64 = self._l1_select_batched(
+                masks, kw, ey_adj, l1_reg)
+            return self._solve_selected(
+                masks, kw, ey_adj, total, support, g64, r64)
+        route = routes.wls_route(kc, m, self.n_out)
+        if route == "kernel":
+            phi = self._buf("phi", (b, m, self.n_out))
+            # wls_mode 'generic' disables the MFMA Gram build by withholding
+            # the packed masks
+            pk = None if kc.wls_mode == "generic" else packed
+            self.ext.wls_solve(masks, kw, ey_adj, total, phi, pk)
+            return phi
+        if route == "gram":
+            # stress shapes: MFMA-tiled Gram build + fp64 solve
+            return self._solve_gram(masks, kw, ey_adj, total)
+        return self._solve_torch(masks, kw, ey_adj, total)
 
     def _solve_gram(self, masks, kw, ey_adj, total):
         """Stress-shape WLS: the S-dependent

@@ -20,6 +20,7 @@ from typing import List, Optional
 import numpy as np
 
 from ..core.sampler import sample_masks
+from ..ops.routes import sharded_predict_route
 from .engine import is_distributed, shard_bounds
 
 __all__ = ["explain_sample_sharded"]
@@ -140,13 +141,11 @@ def _explain_sample_sharded_gpu(
         sub = masks[:, lo:hi]                                 # view, contiguous
         kws = kw[:, lo:hi]
         sub_X = X_dev[i : i + 1]
-        mpad = max(4, (m + 3) // 4 * 4)
-        npad = (gpu.N + 15) // 16 * 16
         if gpu.linear is None:
             # fused MLP kernel on this rank's slice when the predictor is
             # an in-envelope MLPPredictor, else synth + torch module
             ey = gpu._ey_predict_nonlinear(sub, sub_X, varying)
-        elif mpad <= 64 and npad <= 128 and gpu.n_out in (1, 2, 4):
+        elif sharded_predict_route(m, gpu.N, gpu.n_out) == "u8":
             ey = gpu._ey_fused_linear(sub.contiguous(), sub_X, varying)
         else:
             ey = gpu._ey_linear_torch(sub.contiguous(), sub_X, varying)

@@ -290,10 +290,10 @@ def test_fused_km_bucket_split_along_b(e2e, monkeypatch):
     masks, _ = g._device_masks(plan, np.arange(3))
     X_dev = torch.tensor(X[:3], dtype=torch.float32, device="cuda")
     varying = np.arange(D)
-    whole = g._ey_fused_km(masks, X_dev, varying).clone()
+    whole = g.backend.ey_fused(masks, X_dev, varying).clone()
     monkeypatch.setattr(km_pack, "WORKSPACE_BYTES", 1)
-    assert km_pack.instances_per_launch(g.km["pack"], D, D) == 1
-    split = g._ey_fused_km(masks, X_dev, varying)
+    assert km_pack.instances_per_launch(g.backend.pack, D, D) == 1
+    split = g.backend.ey_fused(masks, X_dev, varying)
     assert torch.equal(split, whole)
 
 
