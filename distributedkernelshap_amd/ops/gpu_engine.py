@@ -5,6 +5,7 @@ Per instance-bucket (instances sharing a varying-group pattern):
   enum masks (host, cached per plan)  ──┐
   fill_random_masks  (HIP K2, Philox)  ─┴─> masks (B,S,M) u8 on device
   fused_predict_linear (HIP K3-K6, MFMA)  -> ey (B,S,n_out)   [linear predictor]
+     — or — fused_predict_linear_wide (HIP K4l) -> ey       [linear, 3/5..16 outputs]
      — or — fused_predict_mlp (HIP K4m, MFMA)  -> ey        [MLP predictor]
      — or — fused_predict_trees (HIP K4t)      -> ey        [tree ensemble]
      — or — fused_predict_trees_walk (HIP K4w) -> ey        [deep trees]
@@ -370,6 +371,45 @@ class GpuKernelShap:
         ey = self._buf("ey", (b, s, self.n_out))
         self.ext.fused_predict_linear(
             masks, diff, c["base"], c["wbg"], ey, c["act"])
+        return ey
+
+    def _wide_consts(self):
+        """``_linear_consts`` operands padded to ``routes.pad_out(n_out)``
+        images for the wide kernel, built once: pad images of ``base`` and
+        ``bgp`` are zero (the kernel never reads them)."""
+        w = getattr(self, "_wide_c", None)
+        if w is None:
+            t = self.torch
+            c = self._linear_consts()
+            noutp = routes.pad_out(self.n_out)
+            base = t.zeros(noutp, c["npad"], device=self.device)
+            base[: self.n_out] = c["base"]
+            bgp = t.zeros(self.N, self.n_groups, noutp, device=self.device)
+            bgp[:, :, : self.n_out] = c["bgp"]
+            w = self._wide_c = {"noutp": noutp, "base": base, "bgp": bgp}
+        return w
+
+    def _ey_fused_wide(self, masks, X_dev, varying, vidx_t=None):
+        """K4l: fused MFMA predict for 3 and 5..16 outputs (multi-class
+        softmax), Mpad<=64, Npad<=512. The diff image is streamed through
+        LDS one 16-column slice at a time; see linear_wide_kernels.hip."""
+        t = self.torch
+        b, s, m = masks.shape
+        c, w = self._linear_consts(), self._wide_consts()
+        vidx_t = self._vidx(varying, vidx_t)
+        # pad slots zeroed once at allocation, name keyed by m (as "diff{m}")
+        diff = self._buf(
+            f"diffw{m}", (b, w["noutp"], routes.pad_m(m), c["npad"]),
+            zeroed=True)
+        # build_diff_f32 wants as many xp / bgp images as the buffer has, so
+        # it also writes the (zero) pad images the kernel never reads: at
+        # most 3 of NOUTP images of extra build work per bucket
+        xp = t.nn.functional.pad(
+            self._x_part(X_dev), (0, w["noutp"] - self.n_out))
+        self.ext.build_diff_f32(xp, w["bgp"], vidx_t, diff)
+        ey = self._buf("ey", (b, s, self.n_out))
+        self.ext.fused_predict_linear_wide(
+            masks, diff, w["base"], c["wbg"], ey, c["act"])
         return ey
 
     def _vidx(self, varying, vidx_t=None):
@@ -810,11 +850,19 @@ class GpuKernelShap:
         # on the tiled stress path) per instance
         n_ntiles = (npad + 127) // 128
         per_inst = s * (g + 8 + 4 + 4 * self.n_out) + (1 << 14)
+        wide = (self.linear is not None and g >= 2 and routes.wide_linear_ok(
+            self.engine.kernels, g, self.N, self.n_out))
         if g > 64 or npad > 128:
             per_inst += s * 4 * self.n_out * n_ntiles        # ftpart
-            per_inst += (4 * routes.pad_m(g) * npad
-                         * max(1, self.n_out))               # diff image
+            if not wide:
+                per_inst += (4 * routes.pad_m(g) * npad
+                             * max(1, self.n_out))           # diff image
             per_inst += 8 * g * (g + self.n_out) * 2         # Gram + LU work
+        if wide:
+            # K4l diff image, NOUTP images at any npad (512 KiB an instance
+            # at 16 classes, 64 groups, 128 columns)
+            per_inst += (4 * routes.pad_out(self.n_out) * routes.pad_m(g)
+                         * npad)
         if self.backend is not None:
             per_inst += self.backend.workspace_bytes_per_instance(g)
         return max(1, self._CHUNK_BYTES // per_inst)
@@ -1057,7 +1105,12 @@ class GpuKernelShap:
                 packed = self._buf("packed", (len(ids), plan.nsamples), t.int64)
                 self.ext.pack_masks(masks, packed)
             pairwise = False
-            if self.linear is not None:
+            if self.linear is not None and routes.wide_linear_ok(
+                    kc, m, self.N, self.n_out):
+                # 3 and 5..16 outputs: asked first, since
+                # ``linear_predict_route`` sends these counts to torch
+                ey = self._ey_fused_wide(masks, sub_X, varying)
+            elif self.linear is not None:
                 # the tiled kernels dual-accumulate (p0, p1), and torch's
                 # softmax is relatively accurate: the pairwise logit survives
                 # saturated probabilities there
@@ -1233,9 +1286,29 @@ class GpuKernelShap:
                 masks, kw, ey_adj, l1_reg)
             return self._solve_selected(
                 masks, kw, ey_adj, total, support, g64, r64)
-        route = routes.wls_route(kc, m, self.n_out)
+        chunks = routes.wls_output_chunks(
+            self.linear is not None, ey_adj.shape[2])
+        if len(chunks) == 1:
+            return self._solve_outputs(masks, packed, kw, ey_adj, total)
+        # 9..16 outputs of a linear predictor: the outputs share masks and
+        # weights and differ only in the right-hand side, so each chunk of at
+        # most 8 columns is an independent call of the same solvers
+        return self.torch.cat([
+            self._solve_outputs(
+                masks, packed, kw, ey_adj[..., lo:hi].contiguous(),
+                total[:, lo:hi].contiguous(), tag=f"c{lo}")
+            for lo, hi in chunks], dim=2)
+
+    def _solve_outputs(self, masks, packed, kw, ey_adj, total, tag=""):
+        """The solver ``routes.wls_route`` names for the output columns it
+        is handed (the count comes from ``ey_adj``). ``tag`` keeps the result
+        workspaces of two chunks apart."""
+        kc = self.engine.kernels
+        b, _, m = masks.shape
+        n_out = ey_adj.shape[2]
+        route = routes.wls_route(kc, m, n_out)
         if route == "kernel":
-            phi = self._buf("phi", (b, m, self.n_out))
+            phi = self._buf("phi" + tag, (b, m, n_out))
             # wls_mode 'generic' disables the MFMA Gram build by withholding
             # the packed masks
             pk = None if kc.wls_mode == "generic" else packed
@@ -1262,7 +1335,7 @@ class GpuKernelShap:
         self.ext.pack_masks_words(masks, packedw)
         mm = m - 1
         a64 = self._buf(f"gramA{mm}", (b, mm, mm), t.float64)
-        r64 = self._buf(f"gramR{mm}", (b, mm, self.n_out), t.float64)
+        r64 = self._buf(f"gramR{mm}", (b, mm, ey_adj.shape[2]), t.float64)
         self.ext.wls_gram(packedw, kw, ey_adj, total, a64, r64)
         try:
             w = t.linalg.solve(a64, r64)

@@ -1,5 +1,5 @@
 // Torch bindings for the CDNA4 KernelSHAP kernels (kshap_kernels.hip,
-// mlp_kernels.hip, tree_kernels.hip, km_kernels.hip).
+// linear_wide_kernels.hip, mlp_kernels.hip, tree_kernels.hip, km_kernels.hip).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <c10/hip/HIPStream.h>
@@ -15,6 +15,12 @@ extern "C" int launch_fused_predict_linear(
     const uint8_t* masksU, const float* diff, const float* base, const float* wbg,
     float* ey, int B, int S, int M, int Mpad, int Npad, int n_out, int act,
     hipStream_t stream);
+
+// linear_wide_kernels.hip
+extern "C" int launch_fused_predict_linear_wide(
+    const uint8_t* masksU, const float* diff, const float* base,
+    const float* wbg, float* ey, int B, int S, int M, int Mpad, int Npad,
+    int n_out, int noutp, int act, hipStream_t stream);
 
 extern "C" void launch_synth_chunk(
     const uint8_t* masks, const float* x, const float* bg, const int* col_group,
@@ -183,6 +189,38 @@ void fused_predict_linear(
         wbg.data_ptr<float>(), ey.data_ptr<float>(), B, S, M, Mpad, Npad,
         n_out, (int)act, current_stream());
     TORCH_CHECK(rc == 0, "fused_predict_linear: unsupported shape (Mpad<=64, Npad%16==0, Npad<=128, n_out in {1,2,4})");
+}
+
+void fused_predict_linear_wide(
+    torch::Tensor masks, torch::Tensor diff, torch::Tensor base,
+    torch::Tensor wbg, torch::Tensor ey, int64_t act) {
+    CHECK_DEV(masks); CHECK_DEV(diff); CHECK_DEV(base); CHECK_DEV(wbg); CHECK_DEV(ey);
+    TORCH_CHECK(masks.dtype() == torch::kUInt8, "masks must be u8 (B,S,M)");
+    TORCH_CHECK(diff.dtype() == torch::kFloat32 && base.dtype() == torch::kFloat32
+                && wbg.dtype() == torch::kFloat32 && ey.dtype() == torch::kFloat32,
+                "diff, base, wbg and ey must be float32");
+    TORCH_CHECK(masks.dim() == 3 && diff.dim() == 4 && base.dim() == 2
+                && wbg.dim() == 1 && ey.dim() == 3, "operand ranks");
+    int B = masks.size(0), S = masks.size(1), M = masks.size(2);
+    int noutp = diff.size(1), Mpad = diff.size(2), Npad = diff.size(3);
+    int n_out = ey.size(2);                    // real classes; noutp images
+    TORCH_CHECK(diff.size(0) == B, "diff batch");
+    TORCH_CHECK(M <= Mpad, "M vs Mpad");
+    TORCH_CHECK(ey.size(0) == B && ey.size(1) == S, "ey shape");
+    TORCH_CHECK(base.size(0) == noutp && base.size(1) == Npad, "base shape");
+    TORCH_CHECK(wbg.size(0) == Npad, "wbg shape");
+    // the column-tile slices are staged with 16-byte loads
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(diff.data_ptr<float>()) % 16 == 0,
+                "diff must be 16-byte aligned");
+    int rc = launch_fused_predict_linear_wide(
+        masks.data_ptr<uint8_t>(), diff.data_ptr<float>(), base.data_ptr<float>(),
+        wbg.data_ptr<float>(), ey.data_ptr<float>(), B, S, M, Mpad, Npad,
+        n_out, noutp, (int)act, current_stream());
+    TORCH_CHECK(rc != -2, "fused_predict_linear_wide: the kernel launch was "
+                "rejected by the runtime");
+    TORCH_CHECK(rc == 0, "fused_predict_linear_wide: unsupported shape "
+                "(act in {0,1,2}, 3<=n_out<=16 with ceil4(n_out) diff images, "
+                "Mpad%4==0, Mpad<=64, Npad%16==0, Npad<=512)");
 }
 
 void synth_chunk(
@@ -932,6 +970,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "Philox coalition sampling (K2)");
     m.def("fused_predict_linear", &fused_predict_linear,
           "MFMA fused mask@diff GEMM + activation + background reduce (K3-K6)");
+    m.def("fused_predict_linear_wide", &fused_predict_linear_wide,
+          "Column-tile-streamed fused linear predict for 3..16 outputs (K4l)");
     m.def("build_diff_f32", &build_diff_f32,
           "diff image in the f32 fused-kernel layout");
     m.def("build_diff_bf16", &build_diff_bf16,

@@ -100,6 +100,41 @@ def sharded_predict_route(m: int, N: int, n_out: int) -> str:
     return "torch"
 
 
+def pad_out(n_out: int) -> int:
+    """Class count padded to the widths the wide linear kernel is
+    instantiated for (4, 8, 12, 16)."""
+    return (n_out + 3) // 4 * 4
+
+
+def wide_linear_ok(kc, m: int, N: int, n_out: int) -> bool:
+    """Whether a bucket of a linear predictor with 3, or 5 to 16, outputs
+    runs the column-tile-streamed kernel (K4l). The eager bucket loop asks
+    this first; ``linear_predict_route`` answers 'torch' for these output
+    counts, an fp32 route whatever ``predict_dtype`` says, so the fp32 wide
+    kernel serves the bf16 settings too. ``n_out == 4`` keeps its one-tile
+    kernels."""
+    return bool(
+        kc.fused_predict
+        and kc.predict_dtype in ("fp32",) + _BF16
+        and 3 <= n_out <= 16
+        and n_out != 4
+        and 2 <= m
+        and pad_m(m) <= 64
+        and pad_n(N) <= 512
+    )
+
+
+def wls_output_chunks(linear: bool, n_out: int):
+    """Column ranges ``[(lo, hi), ...]`` of the outputs solved together. The
+    WLS problems of different outputs share masks and weights and differ only
+    in the right-hand side, so 9 to 16 outputs of a linear predictor go
+    through the solvers (at most 8 outputs a call) as two chunks; everything
+    else is one chunk, as before."""
+    if linear and 9 <= n_out <= 16:
+        return [(0, 8), (8, n_out)]
+    return [(0, n_out)]
+
+
 def wls_route(kc, m: int, n_out: int) -> str:
     """'kernel' (K7), 'gram' (MFMA Gram build + fp64 solve) or 'torch'.
     fp32 Gram conditioning degrades with m (Shapley kernel weights span

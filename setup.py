@@ -20,6 +20,7 @@ try:
             sources=[
                 "distributedkernelshap_amd/ops/hip/bindings.cpp",
                 "distributedkernelshap_amd/ops/hip/kshap_kernels.hip",
+                "distributedkernelshap_amd/ops/hip/linear_wide_kernels.hip",
                 "distributedkernelshap_amd/ops/hip/mlp_kernels.hip",
                 "distributedkernelshap_amd/ops/hip/tree_kernels.hip",
                 "distributedkernelshap_amd/ops/hip/tree_walk_kernels.hip",
